@@ -12,8 +12,14 @@ KITTI replay (already resident in HBM):
                                                 Tracking::MonocularInitialization)
   gather of the padded keypoints/descriptors to rank 0 (N > 1)
 
-Prints ONE JSON line on rank 0.  Launch:
-  python bench.py [--steps K --warmup W]                       (1 GPU)
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0 (`value`, `ms_per_step`,
+the configuration, keypoints and matches per frame).  `--dump-outputs DIR` also writes what the last timed step
+computed as DIR/<name>.npy.  `--full` adds, after the timed region and outside `value`, everything else the
+line can carry: the per-stage breakdown from an instrumented second pass, the isolated one-stream pass and the
+rooflines, the achievable-bandwidth probe, the rank-0 ingress proxy, the host-fed leg and the CPU baselines.
+
+Launch:
+  python bench.py [--steps K --warmup W] [--full]              (1 GPU)
   python bench.py --gpus N [...]                               (N GPUs: starts the ranks itself)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Without a launcher (WORLD_SIZE unset), `--gpus N` > 1 starts
@@ -407,6 +413,44 @@ def cpu_scaling(frames: np.ndarray, budget_s: float, max_threads: int):
                                                          info.get("cgroup_cpu_quota") or info["allowed_cpus"])}}
 
 
+DUMP_SAMPLE_BYTES = 48 << 20   # the per-keypoint arrays of --dump-outputs together (64 MB is the limit for all files)
+
+
+def dump_outputs(path, pl, m12, nm):
+    """--dump-outputs: what one step hands its caller, as float32 .npy files under `path`.
+
+    pl is the step's payload (kps int32 (B, cap, 7) = cv::KeyPoint records, desc uint8 (B, cap, 32), counts (B,)),
+    m12 / nm its SearchForInitialization result for the pairs (f, f + 1).  The per-keypoint arrays of a whole batch
+    are far larger than the limit, so they are written for a fixed seeded sample of frames (sample_frames.npy, the
+    same for every run with the same --batch); counts and nmatches are written whole.  Slots at or past a frame's
+    count hold whatever an earlier batch left there: they are written as 0 (matches12: -1).
+      keypoints.npy    (n, cap, 7)   x, y, size, angle, response, octave, class_id of frame sample_frames[i]
+      descriptors.npy  (n, cap, 32)  descriptor bytes
+      matches12.npy    (n, cap)      vnMatches12 of the pair (sample_frames[i], sample_frames[i] + 1)
+      counts.npy (B,), nmatches.npy (B - 1,), sample_frames.npy (n,)"""
+    B, cap = pl.kps.shape[0], pl.kps.shape[1]
+    dev = pl.kps.device
+    n = max(1, min(max(1, B - 1), DUMP_SAMPLE_BYTES // (cap * (7 + 32 + 1) * 4)))
+    idx = np.sort(np.random.default_rng(0).choice(max(1, B - 1), size=n, replace=False))
+    it = torch.from_numpy(idx).to(dev)
+    valid = torch.arange(cap, device=dev)[None, :] < pl.counts[it].to(torch.int64)[:, None]
+    k = pl.kps[it]
+    kf = torch.cat([k[..., :5].contiguous().view(torch.float32), k[..., 5:].to(torch.float32)], dim=2)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    arrays = {
+        "keypoints": torch.where(valid[..., None], kf, zero),
+        "descriptors": torch.where(valid[..., None], pl.desc[it].to(torch.float32), zero),
+        "counts": pl.counts.to(torch.float32),
+        "nmatches": nm.to(torch.float32),
+        "sample_frames": it.to(torch.float32),
+    }
+    if B > 1:
+        arrays["matches12"] = torch.where(valid, m12[it].to(torch.float32), zero - 1)
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")),
@@ -423,6 +467,12 @@ def main():
     ap.add_argument("--streams", type=int, default=2, help="pipeline depth (batches in flight per GPU; "
                     "GPU_MAX_HW_QUEUES=4 leaves 3 besides the default stream; at 4096 frames per step 2 beat 3: "
                     "290.1-295.3k against 287.0-288.3k frames/s)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the instrumented and isolated passes (stage times, rooflines), "
+                         "the copy-bandwidth probe, the rank-0 ingress proxy, the host-fed leg and the CPU baselines; "
+                         "the options below that size those legs only matter with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, see dump_outputs()")
     ap.add_argument("--iso-steps", type=int, default=3, help="untimed one-stream steps for roofline_isolated")
     ap.add_argument("--match-stream", action="store_true",
                     help="SearchForInitialization on the default stream beside the extraction streams")
@@ -533,15 +583,19 @@ def main():
         exs[j].sync(streams[j])   # raises on device-side overflow
     elapsed = t1 - t0
     # results of the last timed step, read now: the host-fed leg below reuses the payloads and m12 / nm
+    jl = (args.warmup + args.steps - 1) % P
     counts = last_payload[0].counts.cpu().numpy()
-    nmatch = nm[(args.warmup + args.steps - 1) % P].cpu().numpy()
+    nmatch = nm[jl].cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_payload[0], m12[jl], nm[jl])
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     used = sorted({(args.warmup + k) % P for k in range(args.steps)})
+    full = args.full
     elapsed_inst = None
-    if not inst:   # the instrumented pass (not part of `value`)
+    if full and not inst:   # the instrumented pass (not part of `value`)
         for e in exs:
             e.set_timing(True)
         torch.cuda.synchronize()
@@ -552,13 +606,15 @@ def main():
         elapsed_inst = time.perf_counter() - ti
         for j in range(P):
             exs[j].sync(streams[j])
-    stage_ms = sum(exs[j].stage_times() for j in used)   # sums over the instrumented steps (all streams)
-    match_ms = sum(a.elapsed_time(b) for a, b in ev_m)
+    stage_ms, match_ms = None, None
+    if full or inst:
+        stage_ms = sum(exs[j].stage_times() for j in used)   # sums over the instrumented steps (all streams)
+        match_ms = sum(a.elapsed_time(b) for a, b in ev_m)
 
     # isolated pass (after the timed region, not part of `value`): the same steps one at a
     # time on one stream, so every kernel's duration is its own (roofline_isolated)
     iso_stage, iso_match = None, None
-    if args.iso_steps > 0 and P > 1:
+    if full and args.iso_steps > 0 and P > 1:
         ev_m.clear()
         exs[0].set_timing(True)
         for k in range(args.iso_steps):
@@ -575,7 +631,7 @@ def main():
     # receive path when it lands a peer's data in a staging buffer and copies it out (a direct P2P write
     # would only add the writes, so this bounds the cost from above).
     ingress = None
-    if world == 1 and args.ingress_peers > 0:
+    if full and world == 1 and args.ingress_peers > 0:
         nbp = hands[0].payloads[0].nbytes
         rbuf = [torch.empty(nbp, dtype=torch.uint8, device=dev) for _ in range(args.ingress_peers)]
         src = torch.empty(nbp, dtype=torch.uint8, device=dev)
@@ -627,7 +683,7 @@ def main():
     # stream uploads batch k into pipeline slot k % P's input buffer while the other slots extract;
     # slot j's buffer is overwritten only after its previous extraction has finished reading it.
     host_fed = None
-    if args.host_steps > 0 and world == 1:   # per-GPU PCIe figure; N > 1 ranks would each pin a 3.8 GB copy
+    if full and args.host_steps > 0 and world == 1:   # per-GPU PCIe figure; N > 1 ranks would each pin a 3.8 GB copy
         hseq = torch.from_numpy(seq).pin_memory()
         # input ring deeper than the pipeline: an upload may run two batches ahead of the oldest extraction
         # still reading its buffer (a slot's extraction lasts about P step times while it shares the chip)
@@ -707,15 +763,17 @@ def main():
     K = args.steps
     frames_total = world * B * K
     value = frames_total / elapsed
-    stages = {"pyramid": float(stage_ms[0]) / K, "fast": float(stage_ms[1]) / K,
-              "quadtree": float(stage_ms[2]) / K, "describe": float(stage_ms[3]) / K,
-              "match": match_ms / K}
+    # the stage breakdown and the rooflines below need per-stage times: --full or --instrument-timed
+    stages = None if stage_ms is None else {
+        "pyramid": float(stage_ms[0]) / K, "fast": float(stage_ms[1]) / K, "quadtree": float(stage_ms[2]) / K,
+        "describe": float(stage_ms[3]) / K, "match": match_ms / K}
     # algorithmic bytes per launch (DESIGN.md "Roofline"): one launch covers B frames
     sizes = level_sizes()
     A = [w * h for w, h in sizes]
     n_cand = None
     try:
-        n_cand = int(sum(len(ex.debug_candidates(0, l)) for l in range(NLEVELS)))
+        if stages is not None:
+            n_cand = int(sum(len(ex.debug_candidates(0, l)) for l in range(NLEVELS)))
     except Exception:
         pass
     kept = float(counts.mean())
@@ -823,14 +881,15 @@ def main():
                             "value_host_fed)",
                    "handback_bytes_per_rank_per_step": hands[0].payloads[0].nbytes,
                    "handback_bytes_to_rank0_per_step": hands[0].payloads[0].nbytes * (world - 1)},
-        "stage_ms_per_step": {k: round(v, 4) for k, v in stages.items()},
-        "stage_timing": "per-stage HIP events in the timed region" if elapsed_inst is None else
-                        "per-stage HIP events in a second pass of the same steps (%.1f frames/s with the events)"
-                        % (world * B * K / elapsed_inst),
         "keypoints_per_frame": round(kept, 1),
         "matches_per_pair": round(float(nmatch.mean()), 1),
-        "roofline": roofline(stages),
     }
+    if stages is not None:
+        out["stage_ms_per_step"] = {k: round(v, 4) for k, v in stages.items()}
+        out["stage_timing"] = ("per-stage HIP events in the timed region" if elapsed_inst is None else
+                               "per-stage HIP events in a second pass of the same steps (%.1f frames/s with the events)"
+                               % (world * B * K / elapsed_inst))
+        out["roofline"] = roofline(stages)
     if host_fed is not None:
         out["value_host_fed"] = host_fed["value"]
         out["host_fed"] = host_fed
@@ -849,14 +908,15 @@ def main():
         out["roofline_pipelined"] = out["roofline"]
         out["roofline"] = dict(roofline(iso), timing="isolated one-stream pass after the timed region "
                                                         "(same batches); see roofline_pipelined")
-    try:   # after the timed region; not part of `value`
-        cbw, cinfo = copy_bandwidth(dev)
-        out["roofline"]["hbm_copy_GBps"] = round(cbw, 1)
-        out["roofline"]["hbm_copy"] = cinfo
-        out["roofline"]["frac_of_copy"] = round(out["roofline"]["achieved"] / cbw, 5)
-    except Exception:
-        pass
-    if world == 1 and not args.no_cpu:
+    if full:
+        try:   # after the timed region; not part of `value`
+            cbw, cinfo = copy_bandwidth(dev)
+            out["roofline"]["hbm_copy_GBps"] = round(cbw, 1)
+            out["roofline"]["hbm_copy"] = cinfo
+            out["roofline"]["frac_of_copy"] = round(out["roofline"]["achieved"] / cbw, 5)
+        except Exception:
+            pass
+    if full and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(seq, args.cpu_seconds)
         out["speedup_vs_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
         if args.cpu_threads > 1:

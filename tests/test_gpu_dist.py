@@ -8,7 +8,7 @@ inside a batch from the ranks' own match results, the pairs that straddle two ba
 matching the handed-back payloads on rank 0's device (the one-frame halo of §8e).
 
 The reference's only concurrency on this path is the left / right extraction threads
-(/root/reference/src/Frame.cc:94-103); the sharding itself has no reference counterpart to compare with."""
+(src/Frame.cc:94-103); the sharding itself has no reference counterpart to compare with."""
 import os
 import socket
 import traceback

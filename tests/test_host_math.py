@@ -7,7 +7,6 @@
 """
 import hashlib
 import os
-import re
 import subprocess
 
 import pytest
@@ -82,11 +81,7 @@ def _pattern_values():
 def test_pattern_table():
     v = _pattern_values()
     assert len(v) == 1024 and min(v) == -13 and max(v) == 12
+    # the digest of the reference's bit_pattern_31_ values (src/ORBextractor.cc), in order and joined by commas:
+    # equal digests mean the same 1024 numbers, so the test needs no copy of the reference beside the repository
     assert hashlib.sha256(",".join(map(str, v)).encode()).hexdigest() == \
         "88df8ca875cc8db56799edd57bb914edad8acb2d48c202b7a464a575b55dbdb8"
-    ref = "/root/reference/src/ORBextractor.cc"
-    if os.path.exists(ref):   # CPU container only: compare with the reference's table text
-        src = open(ref, encoding="utf-8").read()
-        body = src[src.index("bit_pattern_31_[256*4]"):]
-        body = re.sub(r"/\*.*?\*/", "", body[body.index("{") + 1:body.index("};")], flags=re.S)
-        assert [int(x) for x in re.findall(r"-?\d+", body)] == v

@@ -7,5 +7,6 @@ timeout -k 10 300 python -u -m pytest tests -x -q -m gpu --timeout 120 --timeout
 tail -1 gpurun_out/pt_$TAG.log
 bash tools/gpu_sq.sh sq_$TAG | grep -A1 -E "k_fast|k_describe|k_quadtree|k_pyramid" || exit 1
 cd $R
-timeout -k 10 200 python bench.py --no-cpu > gpurun_out/b_$TAG.json 2>gpurun_out/b_$TAG.err || { tail -20 gpurun_out/b_$TAG.err; exit 1; }
-python3 -c "import json; d=json.load(open('gpurun_out/b_$TAG.json')); print(d['value'], d['stage_ms_isolated'])"
+T=$(mktemp -d)
+timeout -k 10 200 python bench.py --full --no-cpu > $T/bench.json 2> $T/bench.err || { tail -20 $T/bench.err; exit 1; }
+python3 -c "import json; d=json.load(open('$T/bench.json')); print(d['value'], d['stage_ms_isolated'])"

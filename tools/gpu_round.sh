@@ -17,7 +17,7 @@ cp $R/gpurun_out/pmc_$TAG/pmc_traffic.json $R/profiles/pmc_traffic.json && cp $R
 bash tools/gpu_sq.sh sq_$TAG > $O/sq.txt 2>&1 || { echo SQ_FAIL; tail -20 $O/sq.txt; exit 1; }
 cp $R/gpurun_out/sq_$TAG/sq_counters.json $R/profiles/sq_counters.json && cp $R/gpurun_out/sq_$TAG/sq_counters.json $O/
 cd $R
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -30 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -30 $O/bench.err; exit 1; }
 cat $O/bench.json
 cd /tmp && export TMPDIR=/tmp
 # one stream: kernel durations are the kernels' own (bench.py's roofline timing)
