@@ -1,5 +1,6 @@
 // liborbx C ABI (include/orbx.h): handle, geometry, workspace and launch
-// sequencing.  Host code; the kernels are in orbx_extract.hip / orbx_match.hip.
+// sequencing.  Host code; the kernels are in orbx_pyramid.hip / orbx_fast.hip / orbx_quadtree.hip /
+// orbx_describe.hip / orbx_match.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -679,19 +680,11 @@ orbx_status orbx_debug_launches(orbx_handle* h, int rows, int cols, int batch, i
     const orbx_status st = ensure_geometry(h, rows, cols);
     if (st != ORBX_OK) return st;
     const Geometry& g = h->geom;
-    int fast = 0;
-    for (int i = 0; i < g.fast_groups; ++i) fast += g.fast_cb[i + 1] > g.fast_cb[i];
-    if (batch <= kLatencyMaxBatch) fast = std::min(fast, 1);   // launch_fast: one launch for small batches
+    // the launchers' own plans; the pyramid's launches each read one level (counts[4]: bit mask)
+    const PyrLaunches pl = pyr_launches(g, batch);
+    FastRun run[kFastMaxRuns];
     QtGroup grp[kQtMaxGroups];
-    // the pyramid's launches each read one level (counts[4]: bit mask): one launch per level from the one
-    // before it
-    const bool fused = batch <= kLatencyMaxBatch && g.pyr_ngroups > 0;   // launch_pyramid's choice
-    int srcmask = (1 << (g.nlevels - 1)) - 1;
-    if (fused) {
-        srcmask = 0;
-        for (int i = 0; i < g.pyr_ngroups; ++i) srcmask |= 1 << g.pg[i].s;
-    }
-    const int c[5] = {fused ? g.pyr_ngroups : g.nlevels - 1, fast, qt_plan(g, batch, grp), 1, srcmask};
+    const int c[5] = {pl.n, fast_plan(g, batch, run), qt_plan(g, batch, grp), 1, pl.srcmask};
     for (int i = 0; i < n; ++i) counts[i] = i < 5 ? c[i] : 0;
     return ORBX_OK;
 }

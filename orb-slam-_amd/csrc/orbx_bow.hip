@@ -17,30 +17,18 @@
 
 #include <type_traits>
 
+#include "orbx_device.hpp"
 #include "orbx_kernels.hpp"
 
 namespace orbx {
 
 constexpr int kBowMaxCand = ORBM_MAX_FEATURES;     // view2 features per node (LDS bitmap per wave, 2 KiB)
 constexpr int kBowWords = kBowMaxCand / 32;
-constexpr int kTH_LOW = 50, kHisto = 30;
+constexpr int kTH_LOW = 50;
 
-__device__ __forceinline__ void bow_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-
-// the same over a fully active wave with DPP row reductions and four readlanes (no LDS round trips)
-__device__ __forceinline__ uint32_t wave_min_dpp(uint32_t v)
+// wave_min_full (orbx_device.hpp) as update_dpp with bound_ctrl off: this kernel's own copy, because the shared
+// mov_dpp form compiles k_bow_nodes to other code
+__device__ __forceinline__ uint32_t bow_wave_min_full(uint32_t v)
 {
     auto dpp_min = [](uint32_t x, auto ctrl) {
         return min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, decltype(ctrl)::value, 0xF, 0xF, false));
@@ -52,16 +40,6 @@ __device__ __forceinline__ uint32_t wave_min_dpp(uint32_t v)
     const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
     const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
     return min(min(r0, r1), min(r2, r3));
-}
-
-__device__ __forceinline__ int bow_rot_bin(float a1, float a2)
-{
-    const float factor = 1.0f / kHisto;   // the reference's 1/HISTO_LENGTH (bins 0..12 used)
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == kHisto) bin = 0;
-    return bin;
 }
 
 // CheckDistEpipolarLine with the FMAs GCC 11 -O3 -march=native forms
@@ -77,12 +55,6 @@ __device__ __forceinline__ bool bow_epipolar(float x1, float y1, float x2, float
     if (den == 0) return false;
     const float dsqr = num * num / den;
     return (double)dsqr < 3.84 * (double)T.sigma2_2[oct2];
-}
-
-__device__ __forceinline__ int ham_u4(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
 // A view with its arrays as global pointers: the struct's pointers are loaded from memory, where the compiler no
@@ -152,7 +124,7 @@ __global__ __launch_bounds__(256) void k_bow_nodes(int mode, const orbm_bow_view
     int* BN = bins + (size_t)p * stride;
     uint32_t* done = s_done[wave];
     for (int i = lane; i < (nb + 31) / 32; i += 64) done[i] = 0;
-    bow_wave_sync();
+    wave_lds_sync();
     const bool tri = mode == ORBM_TRIANGULATION;
     orbm_triang_params T;
     if (tri) T = TP[p];
@@ -228,7 +200,7 @@ __global__ __launch_bounds__(256) void k_bow_nodes(int mode, const orbm_bow_view
                     if (mode == ORBM_BOW_KF_KF) ok = ok && mp2;
                 }
                 if (!ok) continue;
-                const int dist = ham_u4(q0, q1, e0, e1);
+                const int dist = ham256(q0, q1, e0, e1);
                 if (tri) {
                     const bool stereo2 = c > 0 ? (B.u_right ? B.u_right[idx2] >= 0 : false) : c_st2;
                     if (T.only_stereo && !stereo2) continue;
@@ -251,7 +223,7 @@ __global__ __launch_bounds__(256) void k_bow_nodes(int mode, const orbm_bow_view
                     }
                 }
             }
-            const uint32_t wbest = wave_min_dpp(best);
+            const uint32_t wbest = bow_wave_min_full(best);
             if (wbest == 0xFFFFFFFFu) continue;
             const int bdist = (int)(wbest >> 16);
             if (tri) {
@@ -259,13 +231,13 @@ __global__ __launch_bounds__(256) void k_bow_nodes(int mode, const orbm_bow_view
                 if (lane == 0) {
                     const int idx2 = B.fv_idx[b0 + pos];
                     M[idx1] = idx2;
-                    if (check_ori) BN[idx1] = bow_rot_bin(ang1, B.kps[idx2].angle);
+                    if (check_ori) BN[idx1] = rot_bin(ang1, B.kps[idx2].angle);
                 }
                 continue;
             }
             // second best of the whole node = min(the winner lane's second, every other lane's best)
             const int mine = best == wbest ? second : (int)min(best >> 16, 256u);
-            const int bsecond = (int)wave_min_dpp((uint32_t)mine);
+            const int bsecond = (int)bow_wave_min_full((uint32_t)mine);
             const bool accept = (mode == ORBM_BOW_KF_F ? bdist <= kTH_LOW : bdist < kTH_LOW) &&
                                 (float)bdist < nnratio * (float)bsecond;
             if (accept) {
@@ -275,13 +247,13 @@ __global__ __launch_bounds__(256) void k_bow_nodes(int mode, const orbm_bow_view
                     done[pos >> 5] |= 1u << (pos & 31);
                     if (mode == ORBM_BOW_KF_F) {
                         M[idx2] = idx1;
-                        if (check_ori) BN[idx2] = bow_rot_bin(ang1, B.kps[idx2].angle);
+                        if (check_ori) BN[idx2] = rot_bin(ang1, B.kps[idx2].angle);
                     } else {
                         M[idx1] = idx2;
-                        if (check_ori) BN[idx1] = bow_rot_bin(ang1, B.kps[idx2].angle);
+                        if (check_ori) BN[idx1] = rot_bin(ang1, B.kps[idx2].angle);
                     }
                 }
-                bow_wave_sync();
+                wave_lds_sync();
             }
         }
     }

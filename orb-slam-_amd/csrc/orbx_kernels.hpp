@@ -93,7 +93,7 @@ constexpr int kCellsPerWave = ORBX_FAST_CPW;
 // cell_counts flag: the cell's candidates start at its own slot base (it did not fit its wave's output buffer).
 // Otherwise they follow the wave's earlier cells' in one run from the slot base of the wave's first cell
 // (kCellsPerWave consecutive cells of the level above kLatencyMaxBatch frames, one cell below), so a cell's
-// first slot is that base plus the counts of the wave's cells before it (orbx_extract.hip cell_slot_word).
+// first slot is that base plus the counts of the wave's cells before it (orbx_quadtree.hip cell_slot_word).
 constexpr uint32_t kCellDirect = 0x80000000u;
 __host__ __device__ inline int fast_cells_per_wave(int batch) { return batch <= kLatencyMaxBatch ? 1 : kCellsPerWave; }
 // Workgroup size and keypoints per thread of level l's quadtree: level 0 holds most candidates
@@ -115,9 +115,17 @@ __host__ __device__ inline int qt_regcap(const Geometry& g, int l) { return qt_n
 
 // host: K1 small-batch launch groups and their band tables (Geometry::pg) from the resize row tables
 bool pyr_plan(Geometry& g, const int2* yt, std::vector<int4>& bands);
+// K1's launches for a batch: the fused kernel's, one per level group (small batches, where pyr_plan made groups),
+// or one per level from the level before it; their count and the levels they read, as a bit mask
+struct PyrLaunches { bool fused; int n, srcmask; };
+PyrLaunches pyr_launches(const Geometry& g, int batch);
 void launch_pyramid(const Geometry& g, const ExtractBufs& b, const FramePtrs& p, int batch, hipStream_t s);
 size_t pyr_level_lds(const Geometry& g, int l);   // k_pyramid_level's dynamic LDS for level l (>= 1)
 void fast_groups(Geometry& g);   // host: FAST launch groups (cell ranges, LDS sizes)
+// K2's launches for a batch: cells [cb, ce) with per-wave LDS sized for an rw x rh ROI
+struct FastRun { int cb, ce, rw, rh; };
+constexpr int kFastMaxRuns = 2;   // Geometry::fast_groups at most
+int fast_plan(const Geometry& g, int batch, FastRun* out);   // returns the launch count
 void launch_fast(const Geometry& g, const ExtractBufs& b, const FramePtrs& p, int batch, hipStream_t s);
 void launch_quadtree(const Geometry& g, const ExtractBufs& b, int* frame_counts, int batch, hipStream_t s);
 void launch_describe(const Geometry& g, const ExtractBufs& b, const FramePtrs& p, orbx_keypoint* kps,

@@ -10,18 +10,10 @@
 
 #include <algorithm>
 
-#include <type_traits>
-#include <cstdlib>
-
+#include "orbx_device.hpp"
 #include "orbx_kernels.hpp"
 
 namespace orbx {
-
-__device__ __forceinline__ int ham256(const ulonglong2& a0, const ulonglong2& a1, const ulonglong2& b0,
-                                      const ulonglong2& b1)
-{
-    return __popcll(a0.x ^ b0.x) + __popcll(a0.y ^ b0.y) + __popcll(a1.x ^ b1.x) + __popcll(a1.y ^ b1.y);
-}
 
 // ---------------------------------------------------------------------------
 // M3 TOP2: each thread owns one query; targets stream through LDS in tiles of
@@ -228,33 +220,6 @@ constexpr int kSiRankMax = 4096;   // k_si_grid: rank sort up to this many level
 __host__ __device__ inline size_t si_grid_smem(int cap)
 {
     return (size_t)((cap + 3) & ~3) * 4 + (cap > kSiRankMax ? (size_t)(kSiCells + 4) * 4 : 0);
-}
-
-// min over the 64 lanes with DPP row permutations + 4 readlanes (all lanes active)
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
-{
-    v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true));   // row_half_mirror
-    v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true));   // row_mirror
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
-    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
-    const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-    return min(min(a, b), min(c, d));
-}
-
-// orders this wave's LDS accesses (a wave-level barrier for data exchanged through LDS)
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int lanes_below_u64(unsigned long long m)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
 __device__ __forceinline__ int lower_bound_u32(const uint32_t* a, int n, uint32_t v)
@@ -854,7 +819,7 @@ __global__ __launch_bounds__(256) void k_si_greedy(const orbx_keypoint* __restri
                         if (d < b1) {
                             b2 = b1;
                             b1 = d;
-                            bp = (uint32_t)(count + lanes_below_u64(m));
+                            bp = (uint32_t)(count + lanes_below(m));
                             bx = (uint32_t)i2;
                         } else if (d < b2) {
                             b2 = d;
@@ -864,8 +829,8 @@ __global__ __launch_bounds__(256) void k_si_greedy(const orbx_keypoint* __restri
                 count += __popcll(m);
             }
             const uint32_t key = (b1 << 16) | bp;
-            const uint32_t kmin = wave_min_u32(key);
-            const uint32_t sec = wave_min_u32(key == kmin ? b2 : b1);
+            const uint32_t kmin = wave_min_full(key);
+            const uint32_t sec = wave_min_full(key == kmin ? b2 : b1);
             const unsigned long long wm = __ballot(key == kmin);
             const int wl = wm ? (int)__builtin_ctzll(wm) : 0;
             const int sbd = kmin >> 16 >= 0x1FF ? INT_MAX : (int)(kmin >> 16);
@@ -886,23 +851,17 @@ __global__ __launch_bounds__(256) void k_si_greedy(const orbx_keypoint* __restri
     const long long pt2 = clock64();
 #endif
     // rotation bins of every match made (evicted ones included), final vnMatches12
-    const float factor = 1.0f / 30;
     for (int i = lane; i < n10; i += 64) {
         const int b = m12[i];
         if (b < 0) continue;
         if (check_ori) {
-            float rot = ang1[i] - ang2[b];
-            if (rot < 0.0f) rot += 360.0f;
-            int bb = (int)roundf(rot * factor);
-            if (bb == 30) bb = 0;
+            const int bb = rot_bin(ang1[i], ang2[b]);
             bin[i] = (int8_t)bb;
             atomicAdd(&s_hist[bb], 1);
         }
         if (m21[b] != i) m12[i] = -1;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     if (check_ori) {   // ComputeThreeMaxima + removal, src/ORBmatcher.cc:562-580
         // the 30 bins in one LDS read (lane = bin), then three wave maxima of (count, 31 - bin): the
         // sequential scan's first-max-wins order is the smallest bin among equal counts
@@ -933,9 +892,7 @@ __global__ __launch_bounds__(256) void k_si_greedy(const orbx_keypoint* __restri
             if (bb < 0 || bb == ind1 || bb == ind2 || bb == ind3) continue;
             m12[i] = -1;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     int nmatches = 0;   // wave-uniform: ballot counts
     for (int i0 = 0; i0 < n10; i0 += 256) {   // four rows of 64 at a time: their k2 loads in flight together

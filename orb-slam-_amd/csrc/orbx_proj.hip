@@ -15,17 +15,12 @@
 //                  Assignments and claims live in LDS.
 #include <hip/hip_runtime.h>
 
+#include "orbx_device.hpp"
 #include "orbx_kernels.hpp"
 
 namespace orbx {
 
 constexpr int kPjCols = 64, kPjRows = 48;   // FRAME_GRID_COLS / ROWS (include/Frame.h:37-38)
-
-__device__ __forceinline__ int pj_ham(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // J1 as a stable counting sort over the 3072 cells: per-cell counts by LDS atomics (the
 // arrival slot is unordered), an exclusive scan, a scatter, then each feature's stable rank
@@ -326,7 +321,7 @@ __global__ __launch_bounds__(256) void k_pj_points(const orbx_keypoint* __restri
                     const int idx = pj_candidate(w, M, keys, p, K, U);
                     if (idx < 0 || C[idx]) continue;
                     const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)f * cap + idx) * 32);
-                    top64_insert(T64, top_key(top_entry(pj_ham(q0, q1, d[0], d[1]), 0, K[idx].octave, idx), p));
+                    top64_insert(T64, top_key(top_entry(ham256(q0, q1, d[0], d[1]), 0, K[idx].octave, idx), p));
                 }
             }
         }
@@ -343,16 +338,6 @@ __global__ __launch_bounds__(256) void k_pj_points(const orbx_keypoint* __restri
     R.n = T.n;
     R.accept = accept;
     res[mo] = R;
-}
-
-__device__ __forceinline__ unsigned long long pj_wave_min_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long y = __shfl_xor(v, o);
-        v = y < v ? y : v;
-    }
-    return v;
 }
 
 // ---- chunk-parallel, in-order replay of the reference's greedy loop (both searches) ----
@@ -532,12 +517,12 @@ __global__ __launch_bounds__(64) void k_pj_resolve(const orbx_keypoint* __restri
                 const int idx = pj_candidate(w, Mp, keys, p, K, U);
                 if (idx >= 0 && !C[idx] && !taken[idx]) {
                     const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)f * cap + idx) * 32);
-                    key = ((unsigned long long)pj_ham(q0, q1, d[0], d[1]) << 32) | ((unsigned long long)p << 16) |
+                    key = ((unsigned long long)ham256(q0, q1, d[0], d[1]) << 32) | ((unsigned long long)p << 16) |
                           (unsigned)idx;
                 }
             }
-            const unsigned long long c1 = pj_wave_min_u64(key);
-            const unsigned long long c2 = pj_wave_min_u64(key == c1 ? ~0ull : key);
+            const unsigned long long c1 = wave_min_shfl(key);
+            const unsigned long long c2 = wave_min_shfl(key == c1 ? ~0ull : key);
             if (c1 < b1) {   // merge: the multiset top two by (dist, position)
                 b2 = min(b1, c2);
                 b1 = c1;
@@ -777,16 +762,6 @@ __device__ __forceinline__ int ps_threshold(const orbm_pose_params& P)
     return MODE == ORBM_PROJ_LAST_FRAME ? 100 : (MODE == ORBM_PROJ_KEYFRAME ? P.orb_dist : 50);   // TH_HIGH / TH_LOW
 }
 
-__device__ __forceinline__ int ps_rot_bin(float a1, float a2)
-{
-    const float factor = 1.0f / 30;   // 1/HISTO_LENGTH
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == 30) bin = 0;
-    return bin;
-}
-
 using PsResult = TopResult;   // bins filled for the rotation-checked searches
 
 template <int MODE>
@@ -829,9 +804,9 @@ __global__ __launch_bounds__(256) void k_ps_points(const orbx_keypoint* __restri
                     const int idx = ps_candidate<MODE>(w, keys, p, K, U, P);
                     if (idx < 0 || (kSearch && C[idx])) continue;
                     const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)f * cap + idx) * 32);
-                    const int dist = pj_ham(q0, q1, d[0], d[1]);
+                    const int dist = ham256(q0, q1, d[0], d[1]);
                     if (kSearch) {
-                        top64_insert(T64, top_key(top_entry(dist, bins ? ps_rot_bin(M.angle, K[idx].angle) : 0, 0,
+                        top64_insert(T64, top_key(top_entry(dist, bins ? rot_bin(M.angle, K[idx].angle) : 0, 0,
                                                             idx),
                                                   p));
                     } else {
@@ -914,18 +889,18 @@ __global__ __launch_bounds__(64) void k_ps_resolve(const orbx_keypoint* __restri
                 const int idx = ps_candidate<MODE>(w, keys, p, K, U, P);
                 if (idx >= 0 && !C[idx] && !taken[idx]) {
                     const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)f * cap + idx) * 32);
-                    key = ((unsigned long long)pj_ham(q0, q1, d[0], d[1]) << 32) | ((unsigned long long)p << 16) |
+                    key = ((unsigned long long)ham256(q0, q1, d[0], d[1]) << 32) | ((unsigned long long)p << 16) |
                           (unsigned)idx;
                 }
             }
-            const unsigned long long c1 = pj_wave_min_u64(key);
+            const unsigned long long c1 = wave_min_shfl(key);
             b1 = c1 < b1 ? c1 : b1;
         }
         ReplayPick pk{-1, 0, 0};
         if (b1 != ~0ull) {
             pk.g = (int)(b1 & 0xFFFF);
             pk.accept = (int)(b1 >> 32) <= thr;
-            if (rot) pk.bin = ps_rot_bin(Mp.angle, K[pk.g].angle);
+            if (rot) pk.bin = rot_bin(Mp.angle, K[pk.g].angle);
         }
         return pk;
     };
@@ -934,7 +909,7 @@ __global__ __launch_bounds__(64) void k_ps_resolve(const orbx_keypoint* __restri
     uint32_t drop = 0u;   // the bins outside the three maxima
     if (rot) {            // ComputeThreeMaxima (:1679-1723); every match in another bin is undone
         int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < 30; ++i) {
+        for (int i = 0; i < kHisto; ++i) {
             const int h = S.hist[i];
             if (h > max1) { max3 = max2; max2 = max1; max1 = h; ind3 = ind2; ind2 = ind1; ind1 = i; }
             else if (h > max2) { max3 = max2; max2 = h; ind3 = ind2; ind2 = i; }

@@ -11,35 +11,12 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
+#include "orbx_device.hpp"
 #include "orbx_kernels.hpp"
 
 namespace orbx {
 
 constexpr int kStNT = 256;
-
-__device__ __forceinline__ const uint8_t* st_level(const FramePtrs& P, const Geometry* G, int f, int l, int& pitch)
-{
-    if (l == 0) {
-        pitch = P.in_pitch;
-        return P.in + (size_t)f * P.in_fstride;
-    }
-    pitch = G->lv[l].pitch;
-    return P.pyr + (size_t)f * P.pyr_fstride + G->lv[l].pyr_off;
-}
-
-// BORDER_REFLECT_101 index inside the 19-px pad of a level (ComputePyramid :1350-1373)
-__device__ __forceinline__ int st_reflect(int p, int len)
-{
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = p < 0 ? -p : 2 * len - 2 - p;
-    return p;
-}
-
-__device__ __forceinline__ int ham256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 struct StereoLds {
     int* off;          // [rows + 1] bucket offsets (bucket = floor(kpY))
@@ -185,14 +162,14 @@ __global__ __launch_bounds__(kStNT) void k_stereo_match(const Geometry* __restri
              ur - L - w >= -kEdge;
         if (go) {
             int pl, pr;
-            const uint8_t* IL = st_level(PL, G, fl, levelL, pl);
-            const uint8_t* IR = st_level(PR, G, fr, levelL, pr);
+            const uint8_t* IL = level_base(PL, G, fl, levelL, pl);
+            const uint8_t* IR = level_base(PR, G, fr, levelL, pr);
             const bool inner = vy - w >= 0 && vy + w < H && ux - w >= 0 && ux + w < W && ur - L - w >= 0 &&
                                ur + L + w < W;
             auto px = [&](const uint8_t* I, int pitch, int x, int y) -> int {
                 if (!inner) {
-                    x = st_reflect(x, W);
-                    y = st_reflect(y, H);
+                    x = reflect101(x, W);
+                    y = reflect101(y, H);
                 }
                 return I[(size_t)y * pitch + x];
             };

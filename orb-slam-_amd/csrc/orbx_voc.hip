@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "orbx_device.hpp"
 #include "orbx_host.hpp"
 
 struct orbx_vocabulary {
@@ -36,12 +37,6 @@ struct orbx_vocabulary {
 };
 
 namespace orbx {
-
-__device__ __forceinline__ int voc_ham(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 __global__ __launch_bounds__(256) void k_voc_descend(const int* __restrict__ cbegin, const int* __restrict__ child,
                                                      const uint8_t* __restrict__ vdesc, const int* __restrict__ vword,
@@ -61,11 +56,11 @@ __global__ __launch_bounds__(256) void k_voc_descend(const int* __restrict__ cbe
         ++level;
         int best = child[c0];
         const uint4* b = reinterpret_cast<const uint4*>(vdesc + (size_t)best * 32);
-        int best_d = voc_ham(a0, a1, b[0], b[1]);
+        int best_d = ham256(a0, a1, b[0], b[1]);
         for (int c = c0 + 1; c < c1; ++c) {
             const int id = child[c];
             const uint4* e = reinterpret_cast<const uint4*>(vdesc + (size_t)id * 32);
-            const int dd = voc_ham(a0, a1, e[0], e[1]);
+            const int dd = ham256(a0, a1, e[0], e[1]);
             if (dd < best_d) {
                 best_d = dd;
                 best = id;

@@ -51,7 +51,7 @@ def _disassembly():
 def test_hot_kernels_do_not_spill():
     """The extraction kernels (pyramid, FAST, the LDS quadtree forms, describe) hold their state in registers and
     LDS: no scratch (private memory) instruction, which would be per-lane HBM traffic.  Round 5 removed the last
-    spills, in k_quadtree<256,4> and <512,16>, by giving the dynamic LDS a constant base (orbx_extract.hip
+    spills, in k_quadtree<256,4> and <512,16>, by giving the dynamic LDS a constant base (orbx_device.hpp
     dyn_lds)."""
     import re
     spills = {}

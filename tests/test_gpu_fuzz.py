@@ -116,7 +116,7 @@ def test_initialisation_extractor_8000_at_1080p(orbref, cuda):
 def test_phase2_nodes_past_16_bit_sizes(orbref, cuda):
     """A tiny budget on a 2000 x 2000 noise image: about 400k FAST candidates meet at the single root, whose
     four children (about 100k each) go straight into phase 2 (4 + 3 * 4 > N), so phase 2 sorts nodes of more
-    than 0xFFFF keypoints, past the packed (size, creation) key (csrc/orbx_extract.hip, SH_BIG); the
+    than 0xFFFF keypoints, past the packed (size, creation) key (csrc/orbx_quadtree.hip, SH_BIG); the
     (size, creation) order must still be the oracle's."""
     import orbx
     from test_gpu_parity import assert_same_keypoints

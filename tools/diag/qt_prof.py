@@ -22,7 +22,7 @@ for it in range(4):
     if it == 0:
         fn(buf.ctypes.data, 1)
 fn(buf.ctypes.data, 0)
-# round steps (csrc/orbx_extract.hip k_quadtree): A split set + midlines, B count pass, C scans (+ phase-2
+# round steps (csrc/orbx_quadtree.hip k_quadtree): A split set + midlines, B count pass, C scans (+ phase-2
 # kk), D new list, E relabel; gather = g.scan (cell counts loaded and scanned) + g.copy (candidates to registers)
 names = ["gather", "init", "rounds", "A", "g.scan", "retain", "#p1", "#p2", "#wg", "B", "C", "D", "E", "g.copy", "g.owner", "g.load"]
 print("level  " + " ".join("%9s" % n for n in names))

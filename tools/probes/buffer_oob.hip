@@ -2,7 +2,7 @@
 // (soffset)?  A 64-byte descriptor over a 4 KiB buffer of nonzero words; each lane loads its dword at
 // voffset = 4 lane with soffset 0, 64 and 256.  Zeros past byte 64 in every row mean the check covers the
 // sum; data means soffset bypasses it.  k_fast_cells' first staging passes (fast_issue0,
-// orb-slam-_amd/csrc/orbx_extract.hip) rely on the first answer: tests/test_gpu_edges.py runs this probe
+// orb-slam-_amd/csrc/orbx_fast.hip) rely on the first answer: tests/test_gpu_edges.py runs this probe
 // through liboob_probe.so (built by __graft_entry__.build()) on every GPU test pass.
 //   hipcc --offload-arch=gfx950 -O2 -o /tmp/buffer_oob tools/probes/buffer_oob.hip && /tmp/buffer_oob
 //   hipcc --offload-arch=gfx950 -O2 -shared -fPIC -DOOB_PROBE_LIB -o tools/probes/liboob_probe.so tools/probes/buffer_oob.hip
