@@ -159,6 +159,12 @@ orbx_status orbx_get_stage_times(orbx_handle* h, float* ms, int n);
  * reference order (vToDistributeKeys); cand_counts[l]. */
 orbx_status orbx_debug_pyramid(orbx_handle* h, int frame, uint8_t* out, size_t out_size);
 orbx_status orbx_debug_candidates(orbx_handle* h, int frame, int level, int* xys, int cap, int* n);
+/* Test hook: makes the bytes no kernel owns a test input.  Waits for the handle's last work, sets
+ * every byte of the pyramid workspace and of the host path's staged input image (device block and
+ * pinned staging rows), over their whole current capacity, to (uint8_t)value, and synchronises.
+ * Buffers only grow, so the next extraction of a shape the workspace already holds keeps the fill
+ * in every byte it does not write: the row padding of each level and the room past the last level. */
+orbx_status orbx_debug_fill_workspace(orbx_handle* h, int value);
 /* Kernel launches per stage of one batched extract of `batch` frames of rows x cols (measurement
  * hook: per-launch roofline figures): counts[0] pyramid, [1] FAST, [2] quadtree, [3] describe;
  * counts[4]: bit l set if a pyramid launch reads level l. */

@@ -1034,6 +1034,24 @@ orbx_status orbx_debug_candidates(orbx_handle* h, int frame, int level, int* xys
     return k > cap ? ORBX_ENOSPC : ORBX_OK;
 }
 
+orbx_status orbx_debug_fill_workspace(orbx_handle* h, int value)
+{
+    if (!h) return ORBX_EINVAL;
+    DeviceGuard guard(h->device);
+    hipStream_t s = own_stream(h);
+    order_after_last(h, s);
+    const int v = value & 0xFF;
+    if (h->d_pyr && hipMemsetAsync(h->d_pyr, v, cap_of(h, h->d_pyr), s) != hipSuccess) return ORBX_EDEVICE;
+    if (h->d_img && hipMemsetAsync(h->d_img, v, cap_of(h, h->d_img), s) != hipSuccess) return ORBX_EDEVICE;
+    if (hipStreamSynchronize(s) != hipSuccess) return ORBX_EDEVICE;
+    h->done_pending = false;   // everything the handle queued has completed
+    // the staged image is copied whole, row padding included, from the pinned block (orbx_extract): fill the
+    // image rows there too, or the next host call would copy the block's old padding over the fill
+    if (h->h_pin) std::memset(h->h_pin, v, std::min(h->pin_bytes, h->img_bytes));
+    std::fill(h->level_cached.begin(), h->level_cached.end(), false);
+    return ORBX_OK;
+}
+
 }  // extern "C"
 
 namespace {

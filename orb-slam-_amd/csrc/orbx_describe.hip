@@ -181,6 +181,28 @@ __device__ __forceinline__ uint32_t blur_acc(uint32_t C, uint32_t by, uint32_t b
     acc = __builtin_amdgcn_udot2(as_us2(e2), ushort2_t{k1, 34}, acc, false);
     return __builtin_amdgcn_udot2(as_us2(e3), ushort2_t{18, 0}, acc, false);
 }
+// How k_describe stages the 43 x 43 patch of a keypoint at (cx, cy) of level l (w x h pixels, `pitch` bytes per
+// row); the one statement of the choice, for the staging and for the border fix-up (tests/test_describe_borders.py
+// restates it as classify() and asserts that its images put keypoints in every class).
+//   kPatchDma      interior keypoints, and right-border ones whose 43 columns are all inside the level
+//                  (cx + 21 < w): those read up to 9 bytes past the row end, which land in the row padding or in the
+//                  next row of the same level (cy + 22 < h) and only feed blurred columns BRIEF never samples
+//                  (|x| <= 18 + the 3-tap reach).  About 2/3 of the 6.5% of KITTI keypoints the byte path took before.
+//   kPatchBufDma   border keypoints of levels >= 1 whose rows have >= 16 bytes of padding: the same DMA through a
+//                  buffer descriptor over the level's rows; bytes outside the level read as zeros and are repaired
+//                  in LDS.  A 16-byte piece can straddle the descriptor's end only within the level's last 16 bytes,
+//                  which the padding bound makes row padding (a level with less, e.g. 444 px in a 448-byte pitch,
+//                  takes the byte path).  Not for cx < 21 with cy <= 21: there the piece that holds level row 0's
+//                  first pixels starts at offset -4 (0xFFFFFFFC) and the range check does not deliver its in-level
+//                  bytes, which no fix-up repairs (measured: keypoints at (20, 19) got wrong descriptors).
+//   kPatchBytes    the rest (level 0 is the caller's image, with no room around it to read past): reflect-101 bytes.
+enum { kPatchDma = 0, kPatchBufDma = 1, kPatchBytes = 2 };
+__device__ __forceinline__ int desc_patch_path(int l, int cx, int cy, int w, int h, int pitch)
+{
+    if (cx >= 21 && cy >= 21 && cy + 21 < h && (cx + 31 <= w || (cx + 21 < w && cy + 22 < h))) return kPatchDma;
+    if (l > 0 && pitch - w >= 16 && !(cx < 21 && cy <= 21)) return kPatchBufDma;
+    return kPatchBytes;
+}
 #ifndef ORBX_DESC_WPE
 #define ORBX_DESC_WPE 1
 #endif
@@ -271,11 +293,8 @@ __global__ __launch_bounds__(64 * kDescWaves, ORBX_DESC_WPE) void k_describe(con
         const int w = G->lv[l].w, h = G->lv[l].h;
         int pitch;
         const uint8_t* img = level_base(P, G, f, l, pitch);
-        // Interior keypoints, and right-border ones whose 43 columns are all inside the level (cx + 21 < w):
-        // those read up to 9 bytes past the row end, which land in the next row of the same level (cy + 22 < h)
-        // and only feed blurred columns BRIEF never samples (|x| <= 18 + the 3-tap reach).  About 2/3 of the
-        // 6.5% of KITTI keypoints the reflect-101 byte path took before (13% of the describe launch).
-        if (cx >= 21 && cy >= 21 && cy + 21 < h && (cx + 31 <= w || (cx + 21 < w && cy + 22 < h))) {
+        const int path = desc_patch_path(l, cx, cy, w, h, pitch);
+        if (path == kPatchDma) {
             // 16-byte piece c = 64 t + lane of DMA instruction t (global_load_lds_dwordx4: lane L's 16 bytes
             // land at byte 16 L of the instruction's 1 KiB) is piece c % 3 of row c / 3, so three instructions
             // fill rows 0..43 (the third with lanes 0..3 only; row 43 repeats row 42).  Each row's aligned
@@ -297,16 +316,17 @@ __global__ __launch_bounds__(64 * kDescWaves, ORBX_DESC_WPE) void k_describe(con
                     dma_va[t] = o;
                 }
             }
-        } else if (l > 0 && pitch - w >= 16) {
+        } else if (path == kPatchBufDma) {
             // Border keypoints of levels >= 1 (about 5% of KITTI's keypoints, 12% at level 7): the same DMA,
             // through a buffer descriptor over the level's rows (pitch x h bytes of the handle's pyramid block),
-            // so that the patch bytes outside the level read as zeros instead of touching memory (the range check
-            // covers the whole offset: tests/test_gpu_edges.py test_buffer_range_check_covers_soffset); the
-            // reflect-101 bytes are copied in from inside the patch at the loop top (desc_border_fixup).  Offsets
-            // of rows above the level wrap to large unsigned values, also out of range.  A 16-byte chunk can straddle
-            // the descriptor's end only within the level's last 16 bytes, which pitch - w >= 16 makes row padding,
-            // so whether the range check drops such a chunk whole or by dwords, no pixel is lost (a level with
-            // less padding, e.g. 444 px in a 448-byte pitch, takes the byte path below).
+            // so that the patch bytes outside the level read as zeros instead of touching memory; the reflect-101
+            // bytes are copied in from inside the patch at the loop top.  Offsets of rows above the level wrap to
+            // large unsigned values, also out of range.  Every 16-byte piece that holds a pixel the patch uses lies
+            // whole inside the descriptor: desc_patch_path keeps away the keypoints for which one would start before
+            // it or straddle its end.  What pins this is tests/test_describe_borders.py: the oracle's descriptors at
+            // every side and corner this path takes (the last level's bottom-right corner included, whose last pieces
+            // reach the descriptor's end), with the row padding and the bytes past the level set to 0x00, 0xFF and
+            // 0x5A (orbx_debug_fill_workspace); no probe of the range check itself is relied on.
             const long long s0 = (long long)(cy - 21) * pitch + (cx - 21);
             const uint32_t a0 = (uint32_t)(s0 & ~3ll);
             sb = (int)(s0 & 3);
@@ -326,8 +346,8 @@ __global__ __launch_bounds__(64 * kDescWaves, ORBX_DESC_WPE) void k_describe(con
         } else {
             sb = 0;
             sp = 0;
-            // level-0 border keypoints (the caller's image: no room around it to read past) and those of levels
-            // with under 16 bytes of row padding: reflect-101 bytes,
+            // level-0 border keypoints (the caller's image: no room around it to read past), those of levels
+            // with under 16 bytes of row padding and the top-left ones of desc_patch_path: reflect-101 bytes,
             // lane = column (43 of the 48 per row), the column reflection once per lane,
             // the row's per row (wave-uniform), and 11 rows' loads in flight before their LDS stores
             static_assert(kRawRows >= 44, "rows 0..43 filled");
@@ -460,8 +480,8 @@ __global__ __launch_bounds__(64 * kDescWaves, ORBX_DESC_WPE) void k_describe(con
         // whole rows (lane = column), so the corners reflect in both directions.  The patch spans level columns
         // cx - 21 .. cx + 21 and rows cy - 21 .. cy + 21 (patch row 43 repeats row 42), and a keypoint lies >= 19 px
         // inside its level, so one reflection reaches every byte.
-        if (l > 0 && LG.pitch - LG.w >= 16 &&
-            !(cx >= 21 && cy >= 21 && cy + 21 < LG.h && (cx + 31 <= LG.w || (cx + 21 < LG.w && cy + 22 < LG.h)))) {
+        // (kPatchBufDma needs l > 0, where LG.pitch is the pitch fill() staged with)
+        if (desc_patch_path(l, cx, cy, LG.w, LG.h, LG.pitch) == kPatchBufDma) {
             const int w = LG.w, h = LG.h, x0 = cx - 21, y0 = cy - 21;
             auto at = [&](int r, int c) { return raw + r * kRawP + ((csb + r * csp) & 3) + c; };
             if (x0 < 0 || x0 + 42 >= w) {   // wave-uniform

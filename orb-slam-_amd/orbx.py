@@ -38,7 +38,7 @@ BLUR_SCALAR, BLUR_SSE2, BLUR_BITEXACT = 0, 1, 2
 EXPORTED = [
     "orbx_create", "orbx_destroy", "orbx_get_tables", "orbx_capacity", "orbx_set_cv_modes", "orbx_extract", "orbx_get_level",
     "orbx_extract_batch_device", "orbx_extract_stage_device", "orbx_sync", "orbx_set_timing", "orbx_get_stage_times",
-    "orbx_debug_pyramid", "orbx_debug_candidates", "orbx_debug_launches", "orbm_descriptor_distance", "orbm_allpairs_device", "orbm_allpairs",
+    "orbx_debug_pyramid", "orbx_debug_candidates", "orbx_debug_fill_workspace", "orbx_debug_launches", "orbm_descriptor_distance", "orbm_allpairs_device", "orbm_allpairs",
     "orbm_search_init_batch_device", "orbm_search_for_initialization_device", "orbm_search_for_initialization",
     "orbx_compute_stereo_matches", "orbx_stereo_batch_device",
     "orbm_bow_search_device", "orbm_bow_search",
@@ -176,6 +176,7 @@ def _load():
     L.orbx_get_stage_times.argtypes = [vp, f32p, C.c_int]
     L.orbx_debug_pyramid.argtypes = [vp, C.c_int, u8p, C.c_size_t]
     L.orbx_debug_candidates.argtypes = [vp, C.c_int, C.c_int, i32p, C.c_int, i32p]
+    L.orbx_debug_fill_workspace.argtypes = [vp, C.c_int]
     L.orbx_debug_launches.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, C.c_int]
     L.orbm_descriptor_distance.argtypes = [u8p, u8p]
     L.orbm_allpairs_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
@@ -406,6 +407,12 @@ class ORBextractor:
                                                                   out.ctypes.data_as(C.POINTER(C.c_int)), cap,
                                                                   C.byref(n)))
         return out[:n.value].copy()
+
+    def debug_fill_workspace(self, value):
+        """Byte-fill the pyramid workspace and the host path's staged image over their whole capacity, after the
+        handle's last work, and synchronise: the next extraction of a shape the workspace already holds then
+        finds `value` in every byte it does not write itself (row padding, the room past the last level)."""
+        _check("orbx_debug_fill_workspace", lib.orbx_debug_fill_workspace(self._h, int(value) & 0xFF))
 
     def debug_launches(self, rows, cols, batch):
         """Kernel launches per stage of one batched extract: {pyramid, fast, quadtree, describe}, and
