@@ -452,6 +452,44 @@ orbx_status orbm_project_search(int device, int mode, const orbx_keypoint* kps, 
                                 const orbm_map_point* pts, const uint8_t* pdesc, int np,
                                 const orbm_pose_params* params, int* match, int* nmatches);
 
+/* ---- ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) ----
+ * src/ORBmatcher.cc:1170-1394, called by LoopClosing::ComputeSim3 (src/LoopClosing.cc:323, th = 7.5) between
+ * SearchByBoW(KF, KF) and SearchByProjection(pKF, Scw, ...).  Every feature of KF1 with a MapPoint that is not
+ * in vpMatches12 yet goes to camera 1 (R1w, t1w), through sR21 = (1.0/s12)*R12.t(), t21 = -sR21*t12 to camera
+ * 2, and takes the first minimum Hamming distance over KeyFrame::GetFeaturesInArea(u, v, th * scale[level])
+ * among octaves level-1..level, accepted at <= TH_HIGH (:1216-1293); the features of KF2 search KF1 through
+ * sR12 = s12*R12, t12 (:1296-1373); a match stands where both directions agree (:1375-1391).
+ * Both KeyFrames share one orbm_pose_params (the reference uses pKF1's intrinsics for both directions,
+ * :1173-1176); of it only fx, fy, cx, cy, min/max_x/y, grid_*_inv, log_scale, nlevels, scale[] and th are
+ * read.  Per feature an orbm_map_point holds GetMapPointMatches()[i]: x, y, z, max_dist, min_dist and flags
+ * bit 0 = pMP && !pMP->isBad() (all else ignored), with pMP->GetDescriptor() as its descriptor.
+ *
+ * Batched device path.  nkf KeyFrames at stride cap: d_kps / d_desc (mvKeysUn, mDescriptors), d_mps /
+ * d_mpdesc (GetMapPointMatches() per feature and each MapPoint's descriptor), d_counts[nkf],
+ * d_pose[f * 12] row-major 3x4 Tcw.  Pair p: KF1 = d_pair_a[p], KF2 = d_pair_b[p], d_sim3[p * 13] = s12,
+ * R12 (row-major), t12; d_already1[p * cap + i1] = vpMatches12[i1] != NULL on entry, d_already2[p * cap + i2]
+ * = vbAlreadyMatched2[i2] (:1200-1210).  Outputs: d_match12[p * cap + i1] = the KF2 feature whose MapPoint
+ * the call writes into vpMatches12[i1] (:1387), -1 where it writes nothing; d_nfound[p] = the return value;
+ * d_match1 / d_match2 (NULL = not wanted): vnMatch1 / vnMatch2 before the agreement check (:1291, :1371).
+ * Every output row has cap entries, -1 past the KeyFrame's count.  A pair whose s12 is not > 0 or whose
+ * KeyFrame indices are outside [0, nkf) matches nothing.  cap <= ORBM_MAX_FEATURES.  Asynchronous on `stream`. */
+orbx_status orbm_search_by_sim3_device(const orbx_keypoint* d_kps, const uint8_t* d_desc, const orbm_map_point* d_mps,
+                                       const uint8_t* d_mpdesc, const int* d_counts, int nkf, int cap,
+                                       const float* d_pose, const int* d_pair_a, const int* d_pair_b,
+                                       const float* d_sim3, const uint8_t* d_already1, const uint8_t* d_already2,
+                                       int npairs, const orbm_pose_params* params, int* d_match12, int* d_nfound,
+                                       int* d_match1, int* d_match2, void* stream);
+
+/* One pair, host arrays, on HIP device `device`; synchronous.  T1w / T2w: 12 floats (row-major 3x4 Tcw),
+ * R12: 9 floats row-major, t12: 3.  match12 and match1: n1 ints, match2: n2 ints (match1 / match2 may be
+ * NULL).  s12 must be > 0 and every keypoint octave in [0, 16). */
+orbx_status orbm_search_by_sim3(int device, const orbx_keypoint* kps1, const uint8_t* desc1,
+                                const orbm_map_point* mps1, const uint8_t* mpdesc1, const uint8_t* already1, int n1,
+                                const float* T1w, const orbx_keypoint* kps2, const uint8_t* desc2,
+                                const orbm_map_point* mps2, const uint8_t* mpdesc2, const uint8_t* already2, int n2,
+                                const float* T2w, float s12, const float* R12, const float* t12,
+                                const orbm_pose_params* params, int* match12, int* nfound, int* match1, int* match2);
+
 /* ---- Image ingest ----
  * The per-frame preparation in front of ORBextractor::operator():
  *   cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) with the CV_32F maps of initUndistortRectifyMap and the

@@ -1392,6 +1392,100 @@ orbx_status orbm_project_search(int device, int mode, const orbx_keypoint* kps, 
     return c.finish();
 }
 
+orbx_status orbm_search_by_sim3_device(const orbx_keypoint* d_kps, const uint8_t* d_desc, const orbm_map_point* d_mps,
+                                       const uint8_t* d_mpdesc, const int* d_counts, int nkf, int cap,
+                                       const float* d_pose, const int* d_pair_a, const int* d_pair_b,
+                                       const float* d_sim3, const uint8_t* d_already1, const uint8_t* d_already2,
+                                       int npairs, const orbm_pose_params* params, int* d_match12, int* d_nfound,
+                                       int* d_match1, int* d_match2, void* stream)
+{
+    if (nkf < 0 || npairs < 0 || npairs > 65535 || cap <= 0 || cap > ORBM_MAX_FEATURES || !params ||
+        params->nlevels < 1 || params->nlevels > 16)
+        return ORBX_EINVAL;
+    if (npairs == 0) return ORBX_OK;
+    if (nkf == 0 || !d_kps || !d_desc || !d_mps || !d_mpdesc || !d_counts || !d_pose || !d_pair_a || !d_pair_b ||
+        !d_sim3 || !d_already1 || !d_already2 || !d_match12 || !d_nfound)
+        return ORBX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    void* scratch = nullptr;
+    if (hipMallocAsync(&scratch, sim3_scratch_bytes(nkf, npairs, cap), s) != hipSuccess) return ORBX_ENOMEM;
+    launch_search_by_sim3(d_kps, d_desc, d_mps, d_mpdesc, d_counts, nkf, cap, d_pose, d_pair_a, d_pair_b, d_sim3,
+                          d_already1, d_already2, npairs, *params, scratch, d_match12, d_nfound, d_match1, d_match2, s);
+    hipFreeAsync(scratch, s);
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+}
+
+orbx_status orbm_search_by_sim3(int device, const orbx_keypoint* kps1, const uint8_t* desc1,
+                                const orbm_map_point* mps1, const uint8_t* mpdesc1, const uint8_t* already1, int n1,
+                                const float* T1w, const orbx_keypoint* kps2, const uint8_t* desc2,
+                                const orbm_map_point* mps2, const uint8_t* mpdesc2, const uint8_t* already2, int n2,
+                                const float* T2w, float s12, const float* R12, const float* t12,
+                                const orbm_pose_params* params, int* match12, int* nfound, int* match1, int* match2)
+{
+    if (n1 < 0 || n1 > ORBM_MAX_FEATURES || n2 < 0 || n2 > ORBM_MAX_FEATURES || !params || !nfound || !T1w || !T2w ||
+        !R12 || !t12 || !(s12 > 0.0f) || params->nlevels < 1 || params->nlevels > 16)
+        return ORBX_EINVAL;
+    *nfound = 0;
+    if ((n1 > 0 && (!kps1 || !desc1 || !mps1 || !mpdesc1 || !already1 || !match12)) ||
+        (n2 > 0 && (!kps2 || !desc2 || !mps2 || !mpdesc2 || !already2)))
+        return ORBX_EINVAL;
+    for (int i = 0; i < n1; ++i)
+        if (kps1[i].octave < 0 || kps1[i].octave >= 16) return ORBX_EINVAL;
+    for (int i = 0; i < n2; ++i)
+        if (kps2[i].octave < 0 || kps2[i].octave >= 16) return ORBX_EINVAL;
+    for (int i = 0; i < n1; ++i) match12[i] = -1;
+    if (match1)
+        for (int i = 0; i < n1; ++i) match1[i] = -1;
+    if (match2)
+        for (int i = 0; i < n2; ++i) match2[i] = -1;
+    if (n1 == 0 || n2 == 0) return ORBX_OK;
+    // the two KeyFrames as a batch of two at stride cap
+    const int cap = std::max(n1, n2);
+    const size_t c = (size_t)cap;
+    const int head[4] = {n1, n2, 0, 1};   // d_counts[2], d_pair_a[1], d_pair_b[1]
+    float geo[24 + 13];                    // d_pose[2 * 12], d_sim3[13]
+    std::memcpy(geo, T1w, sizeof(float) * 12);
+    std::memcpy(geo + 12, T2w, sizeof(float) * 12);
+    geo[24] = s12;
+    std::memcpy(geo + 25, R12, sizeof(float) * 9);
+    std::memcpy(geo + 34, t12, sizeof(float) * 3);
+    HostCall hc(device);
+    const size_t oh = hc.in(head, sizeof(head));
+    const size_t og = hc.in(geo, sizeof(geo));
+    const size_t ok = hc.in(nullptr, sizeof(orbx_keypoint) * 2 * c);
+    const size_t od = hc.in(nullptr, 32 * 2 * c);
+    const size_t om = hc.in(nullptr, sizeof(orbm_map_point) * 2 * c);
+    const size_t omd = hc.in(nullptr, 32 * 2 * c);
+    const size_t oa = hc.in(nullptr, 2 * c);   // already1[cap], already2[cap]
+    const size_t oo = hc.out(sizeof(int) * (3 * c + 1));   // nfound, match12, match1, match2
+    orbx_status rc = hc.prepare();
+    if (rc != ORBX_OK) return rc;
+    auto pack = [&](size_t off, const void* a, const void* b, size_t elem) {
+        uint8_t* h = hc.host(off);
+        std::memset(h, 0, elem * 2 * c);
+        std::memcpy(h, a, elem * (size_t)n1);
+        std::memcpy(h + elem * c, b, elem * (size_t)n2);
+    };
+    pack(ok, kps1, kps2, sizeof(orbx_keypoint));
+    pack(od, desc1, desc2, 32);
+    pack(om, mps1, mps2, sizeof(orbm_map_point));
+    pack(omd, mpdesc1, mpdesc2, 32);
+    pack(oa, already1, already2, 1);
+    if ((rc = hc.upload()) != ORBX_OK) return rc;
+    const int* dh = hc.dev_as<const int>(oh);
+    const float* dg = hc.dev_as<const float>(og);
+    int* dout = hc.dev_as<int>(oo);
+    rc = orbm_search_by_sim3_device(hc.dev_as<const orbx_keypoint>(ok), hc.dev(od), hc.dev_as<const orbm_map_point>(om),
+                                    hc.dev(omd), dh, 2, cap, dg, dh + 2, dh + 3, dg + 24, hc.dev(oa), hc.dev(oa) + c,
+                                    1, params, dout + 1, dout, dout + 1 + c, dout + 1 + 2 * c, hc.stream());
+    if (rc != ORBX_OK) return rc;
+    hc.fetch(oo, nfound, sizeof(int));
+    hc.fetch(oo + sizeof(int), match12, sizeof(int) * (size_t)n1);
+    hc.fetch(oo + sizeof(int) * (1 + c), match1, sizeof(int) * (size_t)n1);
+    hc.fetch(oo + sizeof(int) * (1 + 2 * c), match2, sizeof(int) * (size_t)n2);
+    return hc.finish();
+}
+
 orbx_status orbx_ingest_batch_device(const uint8_t* d_src, int batch, int rows, int cols, int channels, int rgb,
                                      size_t src_step, size_t src_frame_stride, const float* d_map_x,
                                      const float* d_map_y, int nmaps, int dst_rows, int dst_cols, uint8_t* d_dst,

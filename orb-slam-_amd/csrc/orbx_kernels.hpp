@@ -179,4 +179,12 @@ void launch_pose_search(int mode, const orbx_keypoint* kps, const uint8_t* desc,
                         const orbm_map_point* pts, const uint8_t* pdesc, const int* npts, int pcap,
                         const orbm_pose_params& P, void* scratch, int* match, int* nmatches, hipStream_t s);
 
+// match1 / match2 may be null (kept in scratch)
+size_t sim3_scratch_bytes(int nkf, int npairs, int cap);
+void launch_search_by_sim3(const orbx_keypoint* kps, const uint8_t* desc, const orbm_map_point* mps,
+                           const uint8_t* mpdesc, const int* counts, int nkf, int cap, const float* pose,
+                           const int* pair_a, const int* pair_b, const float* sim3, const uint8_t* already1,
+                           const uint8_t* already2, int npairs, const orbm_pose_params& P, void* scratch, int* match12,
+                           int* nfound, int* match1, int* match2, hipStream_t s);
+
 }  // namespace orbx

@@ -988,4 +988,169 @@ void launch_pose_search(int mode, const orbx_keypoint* kps, const uint8_t* desc,
     }
 }
 
+// =====================================================================================
+// ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (:1170-1394), the mutual
+// search of LoopClosing::ComputeSim3 (src/LoopClosing.cc:323).
+//
+// J1 k_pj_grid     as above, once per KeyFrame of the batch (not per pair)
+// J2 k_s3_points   grid (features, pairs, 2 directions), kSub lanes per feature of the searching
+//                  KeyFrame: its MapPoint goes to its own camera, through the relative Sim3 to the
+//                  other camera, and scans that KeyFrame's window like the Fuse modes (first
+//                  minimum, no claims): vnMatch1 / vnMatch2
+// J3 k_s3_agree    one lane per i1: vnMatch2[vnMatch1[i1]] == i1 (:1375-1391)
+// =====================================================================================
+
+// the second camera of one direction: p3Dc_other = M * p3Dc_own + t (:1186-1189)
+struct S3Rel {
+    float M[9], t[3];
+};
+
+// sim3 = s12, R12 (row-major), t12.  dir 0 (KF1 searches KF2): sR21 = (1.0/s12)*R12.t(), t21 = -sR21*t12;
+// dir 1: sR12 = s12*R12, t12.  MatExpr scales are convertTo with a float alpha (as ps_camera's Scw split).
+__device__ __forceinline__ S3Rel s3_relative(int dir, const float* __restrict__ sim3)
+{
+    S3Rel c;
+    const float s12 = sim3[0];
+    const float* R12 = sim3 + 1;
+    const float* t12 = sim3 + 10;
+    if (dir) {
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k) c.M[3 * r + k] = R12[3 * r + k] * s12 + 0.0f;
+            c.t[r] = t12[r];
+        }
+    } else {
+        const float s = (float)(1.0 / (double)s12);
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k) c.M[3 * r + k] = R12[3 * k + r] * s + 0.0f;
+            c.t[r] = -ps_row(c.M + 3 * r, 1, t12[0], t12[1], t12[2]);
+        }
+    }
+    return c;
+}
+
+// :1226-1257 / :1306-1337; false where the reference `continue`s.  Unlike ps_project the distance
+// test is on cv::norm of the camera-frame point, and there is no viewing-angle test.
+__device__ __forceinline__ bool s3_project(const float* __restrict__ Tsw, const S3Rel& c, const orbm_map_point& M,
+                                           const orbm_pose_params& P, PsWin& w)
+{
+    const float a0 = ps_row(Tsw, 1, M.x, M.y, M.z) + Tsw[3];
+    const float a1 = ps_row(Tsw + 4, 1, M.x, M.y, M.z) + Tsw[7];
+    const float a2 = ps_row(Tsw + 8, 1, M.x, M.y, M.z) + Tsw[11];
+    const float xc = ps_row(c.M, 1, a0, a1, a2) + c.t[0];
+    const float yc = ps_row(c.M + 3, 1, a0, a1, a2) + c.t[1];
+    const float zc = ps_row(c.M + 6, 1, a0, a1, a2) + c.t[2];
+    if (zc < 0.0f) return false;
+    const float invz = (float)(1.0 / (double)zc);
+    const float x = xc * invz, y = yc * invz;
+    const float u = __builtin_fmaf(P.fx, x, P.cx);
+    const float v = __builtin_fmaf(P.fy, y, P.cy);
+    if (!(u >= P.min_x && u < P.max_x && v >= P.min_y && v < P.max_y)) return false;   // IsInImage
+    const float maxD = 1.2f * M.max_dist, minD = 0.8f * M.min_dist;
+    double s = 0.0;
+    s += (double)xc * (double)xc;
+    s += (double)yc * (double)yc;
+    s += (double)zc * (double)zc;
+    const float dist = (float)__builtin_sqrt(s);   // cv::norm(p3Dc2)
+    if (dist < minD || dist > maxD) return false;
+    const int L = ps_predict_scale(M.max_dist, dist, P);
+    w.u = u;
+    w.v = v;
+    w.ur = 0.0f;
+    w.r = P.th * P.scale[L & 15];
+    w.minLevel = L - 1;
+    w.maxLevel = L;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_s3_points(const orbx_keypoint* __restrict__ kps,
+                                                   const uint8_t* __restrict__ desc,
+                                                   const orbm_map_point* __restrict__ mps,
+                                                   const uint8_t* __restrict__ mpdesc, const int* __restrict__ counts,
+                                                   int nkf, int cap, const float* __restrict__ pose,
+                                                   const int* __restrict__ pair_a, const int* __restrict__ pair_b,
+                                                   const float* __restrict__ sim3,
+                                                   const uint8_t* __restrict__ already1,
+                                                   const uint8_t* __restrict__ already2, orbm_pose_params P,
+                                                   const uint32_t* __restrict__ gkeys, int* __restrict__ match1,
+                                                   int* __restrict__ match2)
+{
+    const int p = blockIdx.y, dir = blockIdx.z;
+    const int m = blockIdx.x * (256 / kSub) + threadIdx.x / kSub, sub = threadIdx.x % kSub;
+    if (m >= cap) return;   // uniform over the kSub lanes of a feature, like every branch up to the reduction
+    const size_t po = (size_t)p * cap + m;
+    const int fa = pair_a[p], fb = pair_b[p];
+    const int fs = dir ? fb : fa, ft = dir ? fa : fb;   // the searching KeyFrame and the one searched
+    unsigned long long best = ~0ull;                    // first minimum as (dist, position, index)
+    const bool pair_ok = (unsigned)fa < (unsigned)nkf && (unsigned)fb < (unsigned)nkf && sim3[(size_t)p * 13] > 0.0f;
+    if (pair_ok && m < min(counts[fs], cap) && !(dir ? already2[po] : already1[po])) {
+        const size_t so = (size_t)fs * cap + m;
+        const orbm_map_point M = mps[so];
+        if (M.flags & 1) {
+            const S3Rel c = s3_relative(dir, sim3 + (size_t)p * 13);
+            const uint32_t* keys = gkeys + (size_t)ft * pj_grid_stride(cap);
+            PsWin w;
+            if (s3_project(pose + (size_t)fs * 12, c, M, P, w) && ps_window(w, P, keys, cap)) {
+                const orbx_keypoint* K = kps + (size_t)ft * cap;
+                const uint4* qd = reinterpret_cast<const uint4*>(mpdesc + so * 32);
+                const uint4 q0 = qd[0], q1 = qd[1];
+                for (int cx = w.cx0; cx <= w.cx1; ++cx) {   // GetFeaturesInArea order, rows cy0..cy1 only
+                    const int a = (int)keys[cap + cx * kPjRows + w.cy0], b = (int)keys[cap + cx * kPjRows + w.cy1 + 1];
+                    for (int q = a + sub; q < b; q += kSub) {
+                        const int idx = ps_candidate<ORBM_FUSE_SIM3>(w, keys, q, K, nullptr, P);
+                        if (idx < 0) continue;
+                        const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)ft * cap + idx) * 32);
+                        const unsigned long long key = (unsigned long long)ham256(q0, q1, d[0], d[1]) << 32 |
+                                                       (unsigned long long)q << 16 | (unsigned)idx;
+                        best = key < best ? key : best;
+                    }
+                }
+            }
+        }
+    }
+    best = sub_min_u64(best);
+    if (sub != 0) return;
+    const int r = (best != ~0ull && (int)(best >> 32) <= 100) ? (int)(best & 0xFFFF) : -1;   // TH_HIGH
+    if (dir) match2[po] = r;
+    else match1[po] = r;
+}
+
+__global__ __launch_bounds__(256) void k_s3_agree(const int* __restrict__ match1, const int* __restrict__ match2,
+                                                  int cap, int* __restrict__ match12, int* __restrict__ nfound)
+{
+    const int p = blockIdx.y, i1 = blockIdx.x * 256 + threadIdx.x;
+    int r = -1;
+    if (i1 < cap) {
+        const int idx2 = match1[(size_t)p * cap + i1];   // a key's index: < cap
+        if (idx2 >= 0 && match2[(size_t)p * cap + idx2] == i1) r = idx2;
+        match12[(size_t)p * cap + i1] = r;
+    }
+    const int n = __popcll(__ballot(r >= 0));
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&nfound[p], n);
+}
+
+size_t sim3_scratch_bytes(int nkf, int npairs, int cap)
+{
+    return (size_t)nkf * pj_grid_stride(cap) * 4 + (size_t)nkf * 4 + (size_t)2 * npairs * cap * 4 + 256;
+}
+
+void launch_search_by_sim3(const orbx_keypoint* kps, const uint8_t* desc, const orbm_map_point* mps,
+                           const uint8_t* mpdesc, const int* counts, int nkf, int cap, const float* pose,
+                           const int* pair_a, const int* pair_b, const float* sim3, const uint8_t* already1,
+                           const uint8_t* already2, int npairs, const orbm_pose_params& P, void* scratch, int* match12,
+                           int* nfound, int* match1, int* match2, hipStream_t s)
+{
+    uint32_t* gkeys = (uint32_t*)scratch;
+    int* gn = (int*)(gkeys + (size_t)nkf * pj_grid_stride(cap));
+    int* tmp = gn + nkf;
+    if (!match1) match1 = tmp;
+    if (!match2) match2 = tmp + (size_t)npairs * cap;
+    launch_pj_grid(kps, counts, nkf, cap, P.min_x, P.min_y, P.grid_w_inv, P.grid_h_inv, gkeys, gn, s);
+    hipMemsetAsync(nfound, 0, sizeof(int) * (size_t)npairs, s);
+    hipLaunchKernelGGL(k_s3_points, dim3((cap + 256 / kSub - 1) / (256 / kSub), npairs, 2), dim3(256), 0, s, kps, desc,
+                       mps, mpdesc, counts, nkf, cap, pose, pair_a, pair_b, sim3, already1, already2, P, gkeys, match1,
+                       match2);
+    hipLaunchKernelGGL(k_s3_agree, dim3((cap + 255) / 256, npairs), dim3(256), 0, s, match1, match2, cap, match12,
+                       nfound);
+}
+
 }  // namespace orbx

@@ -112,6 +112,17 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     orbm_project_search(0, ORBM_PROJ_LAST_FRAME, (const orbx_keypoint*)kps.data(), desc.data(), mvuRight.data(),
                         taken.data(), n, pose, mps.data(), pdesc.data(), (int)mps.size(), &P, match.data(), &nmatches);
 
+    // SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
+    std::vector<uint8_t> mpdesc1(n * 32), mpdesc2(n * 32), already1(n), already2(n);
+    std::vector<orbm_map_point> mps1(n), mps2(n);
+    std::vector<int> match12(n);
+    float T1w[12] = {}, T2w[12] = {}, s12 = 1.f, R12[9] = {}, t12[3] = {};
+    int nFound = 0;
+    P.th = 7.5f;
+    orbm_search_by_sim3(0, (const orbx_keypoint*)kps.data(), desc.data(), mps1.data(), mpdesc1.data(), already1.data(),
+                        n, T1w, (const orbx_keypoint*)kps.data(), desc.data(), mps2.data(), mpdesc2.data(),
+                        already2.data(), n, T2w, s12, R12, t12, &P, match12.data(), &nFound, nullptr, nullptr);
+
     // ComputeBoW
     std::vector<int32_t> bw(n), node(n), ptr(n + 1), idx(n);
     std::vector<double> bv(n);
@@ -127,7 +138,7 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     orbm_bow_view b{(const orbx_keypoint*)kps.data(), desc.data(), nullptr, nullptr, n1.data(), p1.data(), i1.data(),
                     n, (int)n1.size()};
     orbm_bow_search(0, ORBM_BOW_KF_F, &a, &b, nullptr, mfNNratio, mbCheckOrientation, match.data(), &nmatches);
-    return dist + nmatches + ngood + nb + nn;
+    return dist + nmatches + ngood + nb + nn + nFound;
 }
 
 }  // namespace

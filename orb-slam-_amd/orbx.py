@@ -44,6 +44,7 @@ EXPORTED = [
     "orbm_bow_search_device", "orbm_bow_search",
     "orbm_search_by_projection_device", "orbm_search_by_projection",
     "orbm_project_search_device", "orbm_project_search", "orbx_ingest_batch_device", "orbx_depth_batch_device",
+    "orbm_search_by_sim3_device", "orbm_search_by_sim3",
     "orbm_best2_csr_device", "orbm_best2_csr", "orbm_stereo_band", "orbm_stereo_band_device",
     "orbv_load_text", "orbv_create", "orbv_destroy", "orbv_info", "orbv_transform", "orbv_transform_batch_device",
 ]
@@ -207,6 +208,10 @@ def _load():
                                              P(PoseParams), vp, vp, vp]
     L.orbm_project_search.argtypes = [C.c_int, C.c_int, vp, u8p, f32p, u8p, C.c_int, f32p, vp, u8p, C.c_int,
                                       P(PoseParams), i32p, i32p]
+    L.orbm_search_by_sim3_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int,
+                                             P(PoseParams), vp, vp, vp, vp, vp]
+    L.orbm_search_by_sim3.argtypes = [C.c_int, vp, u8p, vp, u8p, u8p, C.c_int, f32p, vp, u8p, vp, u8p, u8p, C.c_int,
+                                      f32p, C.c_float, f32p, f32p, P(PoseParams), i32p, i32p, i32p, i32p]
     L.orbx_ingest_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
                                            vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, vp]
     L.orbx_depth_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_float,
@@ -681,6 +686,60 @@ class ORBmatcher:
         prm = PoseParams.from_buffer_copy(params)
         prm.th = float(th)
         return self.project_search(FUSE_SIM3, kf[0], kf[1], kf[2], None, Scw, pts, pdesc, prm, device)
+
+    def search_by_sim3(self, kf1, kf2, already1, already2, T1w, T2w, s12, R12, t12, params, device=0):
+        """SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1170-1394) on host arrays.
+        kf = (mvKeysUn, mDescriptors, mps, mpdesc): mps is MAP_POINT_DTYPE per feature (GetMapPointMatches():
+        x, y, z, max_dist, min_dist, flags bit 0 = pMP && !isBad()), mpdesc each MapPoint's GetDescriptor().
+        already1[i1] = vpMatches12[i1] != NULL, already2 = vbAlreadyMatched2 (:1200-1210); params: PoseParams
+        with th set.  Returns (nFound, match12, vnMatch1, vnMatch2): vpMatches12[i1] = vpMapPoints2[match12[i1]]
+        where match12[i1] >= 0."""
+        f32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        side = []
+        for kf, al in ((kf1, already1), (kf2, already2)):
+            k = np.ascontiguousarray(kf[0], KEYPOINT_DTYPE)
+            side.append((k, np.ascontiguousarray(kf[1], np.uint8), np.ascontiguousarray(kf[2], MAP_POINT_DTYPE),
+                         np.ascontiguousarray(kf[3], np.uint8),
+                         np.ascontiguousarray(al if al is not None else np.zeros(len(k), np.uint8), np.uint8)))
+        T = [np.ascontiguousarray(np.asarray(t, np.float32).reshape(-1)[:12]) for t in (T1w, T2w)]
+        R = np.ascontiguousarray(np.asarray(R12, np.float32).reshape(-1)[:9])
+        t = np.ascontiguousarray(np.asarray(t12, np.float32).reshape(-1)[:3])
+        n1, n2 = len(side[0][0]), len(side[1][0])
+        m12, m1 = np.full(max(n1, 1), -1, np.int32), np.full(max(n1, 1), -1, np.int32)
+        m2 = np.full(max(n2, 1), -1, np.int32)
+        nf = C.c_int(0)
+        prm = PoseParams.from_buffer_copy(params)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        args = []
+        for (k, d, mp, md, al), Tw in zip(side, T):
+            args += [k.ctypes.data, _u8(d), mp.ctypes.data, _u8(md), _u8(al), len(k), f32(Tw)]
+        _check("orbm_search_by_sim3",
+               lib.orbm_search_by_sim3(device, *args, float(s12), f32(R), f32(t), C.byref(prm), i32(m12), C.byref(nf),
+                                       i32(m1), i32(m2)))
+        return nf.value, m12[:n1].copy(), m1[:n1].copy(), m2[:n2].copy()
+
+    def search_by_sim3_batch_device(self, kps, desc, mps, mpdesc, counts, pose, pair_a, pair_b, sim3, already1,
+                                    already2, params, match12=None, nfound=None, match1=None, match2=None,
+                                    stream=None):
+        """Batched device form of search_by_sim3 over KeyFrame pairs: kps (B, cap, 7) int32, desc (B, cap, 32)
+        uint8, mps (B, cap, 12) int32 view of MAP_POINT_DTYPE, mpdesc (B, cap, 32), counts (B,), pose (B, 12)
+        float32 Tcw, pair_a / pair_b (npairs,) int32, sim3 (npairs, 13) float32 = s12, R12, t12, already1 /
+        already2 (npairs, cap) uint8.  match1 / match2: tensors to receive vnMatch1 / vnMatch2, or None.
+        Returns (match12, nfound)."""
+        import torch
+        B, cap = kps.shape[0], kps.shape[1]
+        npairs = pair_a.shape[0]
+        if match12 is None:
+            match12 = torch.empty((npairs, cap), dtype=torch.int32, device=kps.device)
+        if nfound is None:
+            nfound = torch.empty((npairs,), dtype=torch.int32, device=kps.device)
+        prm = PoseParams.from_buffer_copy(params)
+        _check("orbm_search_by_sim3_device",
+               lib.orbm_search_by_sim3_device(_ptr(kps), _ptr(desc), _ptr(mps), _ptr(mpdesc), _ptr(counts), B, cap,
+                                              _ptr(pose), _ptr(pair_a), _ptr(pair_b), _ptr(sim3), _ptr(already1),
+                                              _ptr(already2), npairs, C.byref(prm), _ptr(match12), _ptr(nfound),
+                                              _ptr(match1), _ptr(match2), _stream(stream)))
+        return match12, nfound
 
     def search_for_initialization_batch(self, kps, desc, counts, pair_a, pair_b, rows, cols, window=100,
                                         matches12=None, nmatches=None, stream=None, bounds=None, prev_matched=None):
