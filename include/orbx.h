@@ -512,6 +512,66 @@ orbx_status orbx_depth_batch_device(const void* d_src, int depth_type, int batch
                                     size_t src_step, size_t src_frame_stride, float factor, float* d_dst,
                                     size_t dst_step, size_t dst_frame_stride, void* stream);
 
+/* ---- Frame tail: what the Frame constructors do between the extractor and the matchers ----
+ * (src/Frame.cc:145-197 RGB-D, :212-284 monocular; the stereo constructor's ComputeStereoMatches is above)
+ * and Frame::isInFrustum of Tracking::SearchLocalPoints. */
+
+/* mK and mDistCoef (CV_32F): Camera.fx .. Camera.k3 of the settings file (src/Tracking.cc:55-77). */
+typedef struct { float fx, fy, cx, cy, k1, k2, p1, p2, k3; } orbx_camera;
+
+/* cv::undistortPoints(src, dst, K, D, noArray(), K) on n points (x, y float pairs): OpenCV 3.x's
+ * cvUndistortPoints, 5 fixed-point iterations in double (unpinned against a real OpenCV).
+ * Always undistorts, whatever k1 is.  xy_out may equal xy.  Pure host code, no device. */
+orbx_status orbx_undistort_points(const orbx_camera* cam, const float* xy, int n, float* xy_out);
+
+/* Frame::ComputeImageBounds (src/Frame.cc:587-621): bounds[4] = mnMinX, mnMaxX, mnMinY, mnMaxY, from the
+ * undistorted corners (0,0) (cols,0) (0,rows) (cols,rows), or 0, cols, 0, rows when k1 == 0.  Pure host code. */
+orbx_status orbx_image_bounds(const orbx_camera* cam, int rows, int cols, float* bounds);
+
+/* Frame::UndistortKeyPoints (src/Frame.cc:539-579) over an extract batch ([nframes][cap] keypoints, d_counts):
+ * mvKeysUn[i] = mvKeys[i] with pt undistorted; with k1 == 0.0 the keypoints are copied unchanged whatever the
+ * other coefficients are (:543-547).  d_kps_un may equal d_kps; entries at and past d_counts[f] are not
+ * written.  Asynchronous on `stream`. */
+orbx_status orbx_undistort_batch_device(const orbx_keypoint* d_kps, const int* d_counts, int nframes, int cap,
+                                        const orbx_camera* cam, orbx_keypoint* d_kps_un, void* stream);
+
+/* Frame::ComputeStereoFromRGBD (src/Frame.cc:875-896): d = imDepth.at<float>(kp.pt.y, kp.pt.x) at the
+ * distorted keypoint, both coordinates truncated toward zero; d > 0: mvDepth = d, mvuRight = kpU.pt.x - mbf / d
+ * (kpU = the undistorted keypoint), else both -1.  d_depth is the output layout of orbx_depth_batch_device:
+ * frame f at d_depth + f * depth_frame_stride bytes (not read when nframes == 1), row pitch depth_step bytes.
+ * Outputs d_uright[f * cap + i], d_depth_out[f * cap + i]; entries at and past d_counts[f] are not written.
+ * Keypoints come from the extractor and lie inside rows x cols; one that does not (the reference reads out of
+ * bounds there) gets -1 / -1.  Asynchronous on `stream`. */
+orbx_status orbx_rgbd_stereo_batch_device(const orbx_keypoint* d_kps, const orbx_keypoint* d_kps_un,
+                                          const int* d_counts, int nframes, int cap, const float* d_depth,
+                                          int rows, int cols, size_t depth_step, size_t depth_frame_stride,
+                                          float bf, float* d_uright, float* d_depth_out, void* stream);
+
+/* Host path for one frame (host arrays: n keypoints, a rows x cols float depth image of pitch depth_step bytes),
+ * on HIP device `device`.  ORBX_EINVAL for a keypoint outside the image.  Synchronous. */
+orbx_status orbx_rgbd_stereo(int device, const orbx_keypoint* kps, const orbx_keypoint* kps_un, int n,
+                             const float* depth, int rows, int cols, size_t depth_step, float bf, float* uright,
+                             float* depth_out);
+
+/* Frame::isInFrustum(pMP, viewingCosLimit) (src/Frame.cc:342-398) as Tracking::SearchLocalPoints calls it
+ * (src/Tracking.cc:1203-1230, limit 0.5): d_npts[f] MapPoints of frame f at f * pcap, d_pose[f * 12] = row-major
+ * 3x4 mTcw.  Of an orbm_map_point it reads x, y, z, nx, ny, nz, max_dist, min_dist and flags (bit 0: the
+ * caller's !isBad() && mnLastFrameSeen != mnId; bit 1: Observations() > 0); of params fx, fy, cx, cy, bf,
+ * min/max_x/y, log_scale and nlevels.  Writes the orbm_proj_point array orbm_search_by_projection_device reads:
+ * a point in view gets mTrackProjX / Y / XR, mTrackViewCos, mnTrackScaleLevel and flags = 1 | (flags & 2); a
+ * point out of view, or one with bit 0 clear, all zero but flags = flags & 2.  d_ninview[f] = the number of
+ * points with mbTrackInView set (nToMatch).  Entries at and past d_npts[f] are not written.  Asynchronous on
+ * `stream`. */
+orbx_status orbm_frustum_batch_device(const orbm_map_point* d_pts, const int* d_npts, int nframes, int pcap,
+                                      const float* d_pose, const orbm_pose_params* params, float viewing_cos_limit,
+                                      orbm_proj_point* d_out, int* d_ninview, void* stream);
+
+/* Host path for one frame (host arrays; pose = 12 floats, row-major 3x4 mTcw), on HIP device `device`.
+ * Synchronous. */
+orbx_status orbm_frustum(int device, const orbm_map_point* pts, int np, const float* pose,
+                         const orbm_pose_params* params, float viewing_cos_limit, orbm_proj_point* out,
+                         int* ninview);
+
 /* ---- DBoW2 vocabulary (TemplatedVocabulary, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h) ----
  * Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:521-528, src/KeyFrame.cc:59-66) call
  * transform(descriptors, mBowVec, mFeatVec, 4); the FeatureVector it produces is the

@@ -586,63 +586,13 @@ void launch_proj(const orbx_keypoint* kps, const uint8_t* desc, const float* uri
 // file; the reference's GCC -march=native FMAs are explicit).
 // =====================================================================================
 
-__device__ __forceinline__ int ps_x86_int(double v)   // cvttsd2si: NaN / out of range -> INT_MIN
-{
-    return (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);
-}
-
-__device__ __forceinline__ float ps_row(const float* r, int stride, float x, float y, float z)
-{
-    return (r[0] * x + r[stride] * y) + r[2 * stride] * z;   // OpenCV 3.x gemm small-matrix order
-}
-
-struct PsCam {
-    float R[9], t[3], Ow[3];
-    int fwd, bwd;
-};
-
-__device__ __forceinline__ PsCam ps_camera(int mode, const float* __restrict__ pose, const orbm_pose_params& P)
-{
-    PsCam c;
-    if (mode == ORBM_PROJ_SIM3 || mode == ORBM_FUSE_SIM3) {   // Decompose Scw (:298-303)
-        double d = 0.0;
-        for (int k = 0; k < 3; ++k) d += (double)pose[k] * (double)pose[k];
-        const float scw = (float)__builtin_sqrt(d);
-        const float s = (float)(1.0 / (double)scw);
-        for (int r = 0; r < 3; ++r) {
-            for (int k = 0; k < 3; ++k) c.R[3 * r + k] = pose[4 * r + k] * s + 0.0f;
-            c.t[r] = pose[4 * r + 3] * s + 0.0f;
-        }
-    } else {
-        for (int r = 0; r < 3; ++r) {
-            for (int k = 0; k < 3; ++k) c.R[3 * r + k] = pose[4 * r + k];
-            c.t[r] = pose[4 * r + 3];
-        }
-    }
-    for (int r = 0; r < 3; ++r) c.Ow[r] = -ps_row(c.R + r, 3, c.t[0], c.t[1], c.t[2]);   // -Rcw.t()*tcw
-    c.fwd = c.bwd = 0;
-    if (mode == ORBM_PROJ_LAST_FRAME) {   // tlc = Rlw*twc+tlw (:1409-1417)
-        const float tlc2 = ps_row(pose + 20, 1, c.Ow[0], c.Ow[1], c.Ow[2]) + pose[23];
-        c.fwd = tlc2 > P.b && !P.mono;
-        c.bwd = -tlc2 > P.b && !P.mono;
-    }
-    return c;
-}
+// ps_x86_int, ps_row, PsCam / ps_camera and ps_predict_scale (MapPoint::PredictScale) are shared with
+// Frame::isInFrustum (orbx_frame.hip): orbx_device.hpp
 
 struct PsWin {
     float u, v, r, ur;
     int minLevel, maxLevel, cx0, cx1, cy0, cy1, lo, hi;
 };
-
-// MapPoint::PredictScale (src/MapPoint.cc:385-417)
-__device__ __forceinline__ int ps_predict_scale(float max_dist, float dist, const orbm_pose_params& P)
-{
-    const float ratio = max_dist / dist;
-    int n = ps_x86_int(__builtin_ceil(log((double)ratio) / (double)P.log_scale));
-    if (n < 0) n = 0;
-    else if (n >= P.nlevels) n = P.nlevels - 1;
-    return n;
-}
 
 // the per-MapPoint part before GetFeaturesInArea; false where the reference `continue`s
 template <int MODE>

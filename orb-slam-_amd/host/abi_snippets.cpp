@@ -58,6 +58,29 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     orbx_depth_batch_device(d_depth16, 0, batch, rows, cols, 2 * cols, 2 * rows * cols, mDepthMapFactor, d_depth,
                             4 * cols, 4 * rows * cols, stream);
 
+    // the Frame constructors
+    float fx = 435.2f, fy = 435.2f, cx = 367.2f, cy = 252.2f, k1 = -0.28f, k2 = 0.07f, tp1 = 0.f, tp2 = 0.f, k3 = 0.f;
+    float mbf = 47.9f;
+    const orbx_camera cam{fx, fy, cx, cy, k1, k2, tp1, tp2, k3};   // mDistCoef = k1 k2 p1 p2 k3
+    float bounds[4];
+    orbx_image_bounds(&cam, rows, cols, bounds);
+    const orbm_grid gb{bounds[0], bounds[2], 64.f / (bounds[1] - bounds[0]), 48.f / (bounds[3] - bounds[2])};
+    std::vector<float> xy(2 * (size_t)n);
+    int N = n;
+    orbx_undistort_points(&cam, xy.data(), N, xy.data());
+    orbx_keypoint* d_kps_un = nullptr;
+    const int *d_left = nullptr, *d_right = nullptr;
+    float *d_uright = nullptr, *d_depth_kp = nullptr;
+    int* d_ngood = nullptr;
+    orbx_undistort_batch_device(d_kps, d_counts, batch, cap, &cam, d_kps_un, stream);
+    orbx_stereo_batch_device(h, d_kps, d_desc, d_counts, cap, d_left, d_right, batch / 2, mbf, fx, d_uright, d_depth_kp,
+                             d_ngood, stream);
+    orbx_rgbd_stereo_batch_device(d_kps, d_kps_un, d_counts, batch, cap, d_depth, rows, cols, 4 * cols,
+                                  (size_t)4 * rows * cols, mbf, d_uright, d_depth_kp, stream);
+    std::vector<float> imDepth((size_t)rows * cols), uR(n), dK(n);
+    orbx_rgbd_stereo(0, (const orbx_keypoint*)kps.data(), (const orbx_keypoint*)kps.data(), N, imDepth.data(), rows,
+                     cols, 4 * (size_t)cols, mbf, uR.data(), dK.data());
+
     // section 3: ORBmatcher
     int dist = orbm_descriptor_distance(desc.data(), desc.data() + 32);
     std::vector<Point2f> vbPrevMatched(n);
@@ -80,7 +103,7 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     // ComputeStereoMatches and its coarse stage
     std::vector<float> mvuRight(n, -1.f), mvDepth(n, -1.f), mvScaleFactors(8, 1.f);
     int ngood = 0;
-    float mbf = 47.9f, fx = 435.2f, minD = 0.f, maxD = 435.2f;
+    float minD = 0.f, maxD = 435.2f;
     orbx_compute_stereo_matches(hl, hr, (const orbx_keypoint*)kps.data(), desc.data(), n,
                                 (const orbx_keypoint*)kps.data(), desc.data(), n, mbf, fx, mvuRight.data(),
                                 mvDepth.data(), &ngood);
@@ -111,6 +134,20 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     float pose[24] = {};
     orbm_project_search(0, ORBM_PROJ_LAST_FRAME, (const orbx_keypoint*)kps.data(), desc.data(), mvuRight.data(),
                         taken.data(), n, pose, mps.data(), pdesc.data(), (int)mps.size(), &P, match.data(), &nmatches);
+
+    // Tracking::SearchLocalPoints
+    int np = (int)mps.size(), nToMatch = 0;
+    orbm_frustum(0, mps.data(), np, pose, &P, 0.5f, pts.data(), &nToMatch);
+    const orbm_map_point* d_mps = nullptr;
+    const int* d_npts = nullptr;
+    const float* d_Tcw = nullptr;
+    const uint8_t *d_claimed = nullptr, *d_pdesc = nullptr;
+    orbm_proj_point* d_pts = nullptr;
+    int *d_ntomatch = nullptr, *d_match = nullptr, *d_nmatches = nullptr;
+    int pcap = 4000;
+    orbm_frustum_batch_device(d_mps, d_npts, nframes, pcap, d_Tcw, &P, 0.5f, d_pts, d_ntomatch, stream);
+    orbm_search_by_projection_device(d_kps_un, d_desc, d_uright, d_claimed, d_counts, nframes, cap, d_pts, d_pdesc,
+                                     d_npts, pcap, &prm, d_match, d_nmatches, stream);
 
     // SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
     std::vector<uint8_t> mpdesc1(n * 32), mpdesc2(n * 32), already1(n), already2(n);

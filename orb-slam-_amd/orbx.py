@@ -45,6 +45,8 @@ EXPORTED = [
     "orbm_search_by_projection_device", "orbm_search_by_projection",
     "orbm_project_search_device", "orbm_project_search", "orbx_ingest_batch_device", "orbx_depth_batch_device",
     "orbm_search_by_sim3_device", "orbm_search_by_sim3",
+    "orbx_undistort_points", "orbx_image_bounds", "orbx_undistort_batch_device", "orbx_rgbd_stereo_batch_device",
+    "orbx_rgbd_stereo", "orbm_frustum_batch_device", "orbm_frustum",
     "orbm_best2_csr_device", "orbm_best2_csr", "orbm_stereo_band", "orbm_stereo_band_device",
     "orbv_load_text", "orbv_create", "orbv_destroy", "orbv_info", "orbv_transform", "orbv_transform_batch_device",
 ]
@@ -149,6 +151,15 @@ def pose_params(K, bounds, scale, inv_sigma2=None, log_scale=None, bf=0.0, th=1.
     return pp
 
 
+class Camera(C.Structure):
+    """orbx_camera: mK and mDistCoef (CV_32F), Camera.fx .. Camera.k3 of the settings file."""
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
+def camera(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+    return Camera(fx, fy, cx, cy, k1, k2, p1, p2, k3)
+
+
 class _Params(C.Structure):
     _fields_ = [("nfeatures", C.c_int), ("scale_factor", C.c_float), ("nlevels", C.c_int),
                 ("ini_th_fast", C.c_int), ("min_th_fast", C.c_int)]
@@ -216,6 +227,15 @@ def _load():
                                            vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, vp]
     L.orbx_depth_batch_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_float,
                                           vp, C.c_size_t, C.c_size_t, vp]
+    L.orbx_undistort_points.argtypes = [P(Camera), f32p, C.c_int, f32p]
+    L.orbx_image_bounds.argtypes = [P(Camera), C.c_int, C.c_int, f32p]
+    L.orbx_undistort_batch_device.argtypes = [vp, vp, C.c_int, C.c_int, P(Camera), vp, vp]
+    L.orbx_rgbd_stereo_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_size_t,
+                                                C.c_size_t, C.c_float, vp, vp, vp]
+    L.orbx_rgbd_stereo.argtypes = [C.c_int, vp, vp, C.c_int, f32p, C.c_int, C.c_int, C.c_size_t, C.c_float, f32p,
+                                   f32p]
+    L.orbm_frustum_batch_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, P(PoseParams), C.c_float, vp, vp, vp]
+    L.orbm_frustum.argtypes = [C.c_int, vp, C.c_int, f32p, P(PoseParams), C.c_float, vp, i32p]
     L.orbm_best2_csr_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     L.orbm_best2_csr.argtypes = [C.c_int, u8p, C.c_int, u8p, C.c_int, i32p, i32p, C.c_int, i32p, i32p, i32p]
     L.orbm_stereo_band.argtypes = [C.c_int, vp, u8p, C.c_int, vp, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_float,
@@ -484,6 +504,100 @@ def depth_batch_device(src, factor, out=None, stream=None):
                                        src.stride(0) * esz, factor, _ptr(out), out.stride(1) * 4, out.stride(0) * 4,
                                        _stream(stream)))
     return out
+
+
+def _f32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def undistort_points(cam, xy):
+    """cv::undistortPoints(xy, K, D, noArray(), K) (orbx_undistort_points, host code): xy (n, 2) float32."""
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    out = np.empty_like(xy)
+    _check("orbx_undistort_points", lib.orbx_undistort_points(C.byref(cam), _f32p(xy), len(xy), _f32p(out)))
+    return out
+
+
+def image_bounds(cam, rows, cols):
+    """Frame::ComputeImageBounds: (mnMinX, mnMaxX, mnMinY, mnMaxY) as float32 (host code)."""
+    b = np.zeros(4, np.float32)
+    _check("orbx_image_bounds", lib.orbx_image_bounds(C.byref(cam), rows, cols, _f32p(b)))
+    return b
+
+
+def undistort_batch_device(kps, counts, cam, out=None, stream=None):
+    """Frame::UndistortKeyPoints over an extract batch: kps (B, cap, 7) int32, counts (B,).  out: the
+    tensor to receive mvKeysUn (may be kps itself; default a new one, whose rows past the count are
+    uninitialised).  Returns out."""
+    import torch
+    if out is None:
+        out = torch.empty_like(kps)
+    _check("orbx_undistort_batch_device",
+           lib.orbx_undistort_batch_device(_ptr(kps), _ptr(counts), kps.shape[0], kps.shape[1], C.byref(cam),
+                                           _ptr(out), _stream(stream)))
+    return out
+
+
+def rgbd_stereo_batch_device(kps, kps_un, counts, depth, bf, uright=None, depth_out=None, stream=None):
+    """Frame::ComputeStereoFromRGBD over an extract batch: kps / kps_un (B, cap, 7) int32 (mvKeys /
+    mvKeysUn), counts (B,), depth (B, H, W) float32 (depth_batch_device's output; any row / frame
+    stride).  Returns (mvuRight, mvDepth), float32 (B, cap), written below each frame's count."""
+    import torch
+    B, cap = kps.shape[0], kps.shape[1]
+    if uright is None:
+        uright = torch.empty((B, cap), dtype=torch.float32, device=kps.device)
+    if depth_out is None:
+        depth_out = torch.empty((B, cap), dtype=torch.float32, device=kps.device)
+    _check("orbx_rgbd_stereo_batch_device",
+           lib.orbx_rgbd_stereo_batch_device(_ptr(kps), _ptr(kps_un), _ptr(counts), B, cap, _ptr(depth),
+                                             depth.shape[1], depth.shape[2], depth.stride(1) * 4,
+                                             depth.stride(0) * 4, bf, _ptr(uright), _ptr(depth_out),
+                                             _stream(stream)))
+    return uright, depth_out
+
+
+def rgbd_stereo(kps, kps_un, depth, bf, device=0):
+    """Frame::ComputeStereoFromRGBD on host arrays (one frame): returns (mvuRight, mvDepth)."""
+    k = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+    ku = np.ascontiguousarray(kps_un, KEYPOINT_DTYPE)
+    d = np.ascontiguousarray(depth, np.float32)
+    n = len(k)
+    ur, dp = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+    _check("orbx_rgbd_stereo",
+           lib.orbx_rgbd_stereo(device, k.ctypes.data, ku.ctypes.data, n, _f32p(d), d.shape[0], d.shape[1],
+                                d.strides[0], bf, _f32p(ur), _f32p(dp)))
+    return ur[:n].copy(), dp[:n].copy()
+
+
+def frustum_batch_device(pts, npts, pose, params, viewing_cos_limit=0.5, out=None, ninview=None, stream=None):
+    """Frame::isInFrustum over a batch: pts (B, pcap, 12) int32 view of MAP_POINT_DTYPE, npts (B,), pose
+    (B, 12) float32 mTcw, params: PoseParams.  Returns (proj, ninview): proj (B, pcap, 6) int32 view of
+    PROJ_POINT_DTYPE, the d_pts of ORBmatcher's search_by_projection device call, written below each
+    frame's npts; ninview (B,) = nToMatch."""
+    import torch
+    B, pcap = pts.shape[0], pts.shape[1]
+    if out is None:
+        out = torch.empty((B, pcap, 6), dtype=torch.int32, device=pts.device)
+    if ninview is None:
+        ninview = torch.empty((B,), dtype=torch.int32, device=pts.device)
+    prm = PoseParams.from_buffer_copy(params)
+    _check("orbm_frustum_batch_device",
+           lib.orbm_frustum_batch_device(_ptr(pts), _ptr(npts), B, pcap, _ptr(pose), C.byref(prm),
+                                         viewing_cos_limit, _ptr(out), _ptr(ninview), _stream(stream)))
+    return out, ninview
+
+
+def frustum(pts, pose, params, viewing_cos_limit=0.5, device=0):
+    """Frame::isInFrustum on host arrays (one frame): pts MAP_POINT_DTYPE, pose 3x4 mTcw.  Returns
+    (proj PROJ_POINT_DTYPE[np], nToMatch)."""
+    pp = np.ascontiguousarray(pts, MAP_POINT_DTYPE)
+    ps = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(-1)[:12])
+    out = np.zeros(max(len(pp), 1), PROJ_POINT_DTYPE)
+    nv = C.c_int(0)
+    prm = PoseParams.from_buffer_copy(params)
+    _check("orbm_frustum", lib.orbm_frustum(device, pp.ctypes.data, len(pp), _f32p(ps), C.byref(prm),
+                                            viewing_cos_limit, out.ctypes.data, C.byref(nv)))
+    return out[:len(pp)].copy(), nv.value
 
 
 TIE_FIRST, TIE_LAST = 0, 1
