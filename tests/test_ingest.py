@@ -9,6 +9,16 @@ restatement and known answers (identity maps copy exactly, half-pixel shifts ave
 rounding up, pure primaries give the integer coefficients); maps hold integer, tie (k + 1/64),
 out-of-range, NaN and huge coordinates.  GPU: liborbx batch path against the oracle, then
 ingest -> extract against the oracle chain.
+
+What these GPU tests do not reach: launch_ingest switches the kernel's interior fast path off
+(xlim = 0) when the source base, pitch or frame stride is not 4-byte aligned.  cols = 162 gives a
+pitch of 162 (1 channel) or 486 (3 channels) bytes, both 2 mod 4, so test_gpu_ingest_batch runs the
+fast path for 4 channels only, and its border pixels are random draws.  test_ingest_taps.py closes
+that: a tap atlas enumerates every integer position from 3 outside to 3 outside on both axes with
+fractions {0, 1, 16, 31}^2, all 32 x 32 fractions at one position of each border class, the
+k + 1/2 ties (carry and -0 included) and the NaN / inf / huge coordinates, and runs it for every
+(channels, order) over cols 1..17, rows 1, 2, 5 and aligned, padded, offset and odd-pitch source
+layouts, with CPU assertions that each path (fast, aligned window, per-byte) and byte phase is hit.
 """
 import numpy as np
 import pytest
