@@ -608,6 +608,85 @@ orbx_status orbv_transform_batch_device(const orbx_vocabulary* v, const uint8_t*
                                         double* d_bow_weight, int* d_bow_n, int32_t* d_fv_node, int32_t* d_fv_ptr,
                                         int32_t* d_fv_idx, int* d_fv_nnodes, void* stream);
 
+/* ---- KeyFrameDatabase (src/KeyFrameDatabase.cc) and TemplatedVocabulary::score ----
+ * The step between orbv_transform* and the candidate-driven searches above: which keyframes to hand to
+ * SearchByBoW.  BowVectors are what orbv_transform writes: int32_t word ids ascending, double weights.
+ * Only L1_NORM (scoring 0) is served, the scoring ORBvoc carries and ORB_SLAM2 never changes: the other DBoW2
+ * scorings sum vi * wi products, whose FMA contraction in the reference's -O3 -march=native build is not pinned,
+ * and KL needs log.  orbv_score with another scoring and orbv_db_create on another vocabulary return ORBX_EINVAL.
+ *
+ * Limits: qn and every keyframe's n <= ORBV_MAX_FEATURES; at most ORBV_DB_MAX_KEYFRAMES slots between clears,
+ * erased ones included (ORBX_ENOSPC from add beyond).  Word ids must lie in [0, nwords) and ascend strictly; the
+ * host entry points check this (ORBX_EINVAL), the _device forms take the transform's output as it is.
+ * Threading: calls on one database serialise on an internal mutex, as the reference's mMutex does (Tracking,
+ * LocalMapping and LoopClosing all call it).  The database owns a non-blocking stream for its storage; the
+ * synchronous calls run on the pooled streams of the other host calls; every call leaves the caller's current
+ * device as found. */
+#define ORBV_DB_MAX_KEYFRAMES 65536
+
+/* TemplatedVocabulary::score -> L1Scoring::score (ScoringObject.cpp:23-68).  Pure host code, no device. */
+orbx_status orbv_score(int scoring, const int32_t* word1, const double* weight1, int n1, const int32_t* word2,
+                       const double* weight2, int n2, double* score);
+
+typedef struct orbv_database orbv_database;
+/* KeyFrameDatabase(voc), on the vocabulary's device.  reserve_* = initial room (0 = defaults); storage grows on
+ * demand (doubling, device-to-device copies). */
+orbx_status orbv_db_create(const orbx_vocabulary* v, int reserve_keyframes, int reserve_words, orbv_database** out);
+void orbv_db_destroy(orbv_database* db);
+/* KeyFrameDatabase::add (:40-46): returns the keyframe's slot = its position in add order (0, 1, ...).  The
+ * slot's mLoopScore / mRelocScore start at 0.0f.  Synchronous. */
+orbx_status orbv_db_add(orbv_database* db, const int32_t* bow_word, const double* bow_weight, int n, int* slot);
+/* The same for frames 0..nframes-1 of an orbv_transform_batch_device result (f * cap layout), slots[nframes] out
+ * (host, may be NULL).  Waits on `stream` for the nframes counts and for the copy (keyframe insertion is not a
+ * per-frame path). */
+orbx_status orbv_db_add_batch_device(orbv_database* db, const int32_t* d_bow_word, const double* d_bow_weight,
+                                     const int* d_bow_n, int nframes, int cap, int* slots, void* stream);
+/* KeyFrameDatabase::erase (:48-67): the slot keeps its number and its storage until clear; it never shares a
+ * word again and so is skipped as a neighbour. */
+orbx_status orbv_db_erase(orbv_database* db, int slot);
+/* KeyFrameDatabase::clear (:69-73): slots restart at 0. */
+orbx_status orbv_db_clear(orbv_database* db);
+/* nslots: slots handed out since the last clear; nlive: those not erased; words_stored: BowVector entries held. */
+orbx_status orbv_db_info(const orbv_database* db, int* nslots, int* nlive, size_t* words_stored);
+/* LoopClosing::DetectLoop's reference-score loop (src/LoopClosing.cc:124-138): score(query, slot) as double for
+ * each listed slot (an erased slot scores 0); the caller skips isBad() and takes the min as float. */
+orbx_status orbv_db_scores(orbv_database* db, const int32_t* q_word, const double* q_weight, int qn, const int* slots,
+                           int ns, double* scores);
+/* DetectLoopCandidates(pKF, minScore) (:76-197) / DetectRelocalizationCandidates(F) (:199-309).  With nslots the
+ * database's slot count:
+ *   connected[nslots]   spConnectedKeyFrames.count(slot); NULL = none.
+ *   covis[nslots * 10]  GetBestCovisibilityKeyFrames(10) of each slot as slots, in that order, padded with -1; a
+ *                       neighbour that is not in the database is -1; NULL = no neighbours.
+ *   cand[cap]           vpLoopCandidates / vpRelocCandidates as slots, in the reference's order; ORBX_ENOSPC with
+ *                       *ncand set (and the first cap candidates written) when cap is too small.
+ *   words[nslots]       (optional) mnLoopWords / mnRelocWords of the slots in lKFsSharingWords, 0 for every other
+ *                       slot (the reference leaves 1 in a connected keyframe and never reads it).
+ *   scores[nslots]      (optional) mLoopScore / mRelocScore of every slot as the reference's keyframes hold them
+ *                       after the call.  They are per-slot state of the database and persist across queries:
+ *                       DetectRelocalizationCandidates adds pKF2->mRelocScore of any neighbour that merely shares
+ *                       a word (:273-276), scored in this query or not, so it reads what an earlier query left.
+ *                       That stale read is reproduced; where the reference's member is indeterminate (never
+ *                       scored) it is 0.0f here (set by add).  The loop form asks mnLoopWords > minCommonWords of
+ *                       a neighbour and so only reads fresh scores.
+ * Synchronous. */
+orbx_status orbv_db_detect_loop(orbv_database* db, const int32_t* q_word, const double* q_weight, int qn,
+                                const uint8_t* connected, const int32_t* covis, float min_score, int* cand, int cap,
+                                int* ncand, int* words, float* scores);
+orbx_status orbv_db_detect_reloc(orbv_database* db, const int32_t* q_word, const double* q_weight, int qn,
+                                 const int32_t* covis, int* cand, int cap, int* ncand, int* words, float* scores);
+/* _device forms: every pointer a device pointer, the query being one frame of a transform batch (its d_bow_word /
+ * d_bow_weight rows of q_cap entries and its count d_qn -> one int, clamped to q_cap <= ORBV_MAX_FEATURES).
+ * nslots = the database's slot count (ORBX_EINVAL otherwise); d_cand has nslots entries, d_ncand one; d_words /
+ * d_scores (nslots each) may be NULL.  Asynchronous on `stream`; no host read of any result.  Later calls on the
+ * database, on any stream, are ordered behind it. */
+orbx_status orbv_db_detect_loop_device(orbv_database* db, const int32_t* d_q_word, const double* d_q_weight,
+                                       const int* d_qn, int q_cap, const uint8_t* d_connected,
+                                       const int32_t* d_covis, float min_score, int nslots, int* d_cand,
+                                       int* d_ncand, int* d_words, float* d_scores, void* stream);
+orbx_status orbv_db_detect_reloc_device(orbv_database* db, const int32_t* d_q_word, const double* d_q_weight,
+                                        const int* d_qn, int q_cap, const int32_t* d_covis, int nslots, int* d_cand,
+                                        int* d_ncand, int* d_words, float* d_scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,9 @@ __global__ __launch_bounds__(kVocNT) void k_voc_vectors(const int* __restrict__ 
     }
 }
 
+// the HIP ordinal a vocabulary lives on (the KeyFrameDatabase built over it, orbx_kfdb.hip)
+int voc_device(const orbx_vocabulary* v) { return v->device; }
+
 }  // namespace orbx
 
 namespace {

@@ -167,6 +167,34 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     orbv_transform(vocab_handle, desc.data(), n, 4, bw.data(), bv.data(), &nb, node.data(), ptr.data(), idx.data(),
                    &nn);
 
+    // KeyFrameDatabase: add / erase / DetectLoop's reference scores / DetectLoopCandidates / DetectRelocalizationCandidates
+    orbv_database* db = nullptr;
+    orbv_db_create(vocab_handle, 0, 0, &db);
+    int slot = -1, nslots = 0, nlive = 0, ncand = 0;
+    size_t stored = 0;
+    orbv_db_add(db, bw.data(), bv.data(), nb, &slot);
+    orbv_db_info(db, &nslots, &nlive, &stored);
+    std::vector<uint8_t> connected(nslots);
+    std::vector<int32_t> covis(nslots * 10, -1);
+    std::vector<int> cand(nslots), slots(nslots), words(nslots);
+    std::vector<double> ref_scores(nslots);
+    std::vector<float> kf_scores(nslots);
+    double s12score = 0.0;
+    orbv_score(0, bw.data(), bv.data(), nb, bw.data(), bv.data(), nb, &s12score);
+    orbv_db_scores(db, bw.data(), bv.data(), nb, slots.data(), nslots, ref_scores.data());
+    orbv_db_detect_loop(db, bw.data(), bv.data(), nb, connected.data(), covis.data(), (float)ref_scores[0], cand.data(),
+                        nslots, &ncand, words.data(), kf_scores.data());
+    orbv_db_detect_reloc(db, bw.data(), bv.data(), nb, covis.data(), cand.data(), nslots, &ncand, nullptr, nullptr);
+    // replay: the BowVectors of a transform batch and its queries stay on the device
+    int32_t* d_bw = nullptr; double* d_bv = nullptr; int* d_bn = nullptr; int* d_cand = nullptr; int* d_ncand = nullptr;
+    orbv_db_add_batch_device(db, d_bw, d_bv, d_bn, 1, n, slots.data(), stream);
+    orbv_db_detect_loop_device(db, d_bw, d_bv, d_bn, n, nullptr, nullptr, 0.05f, nslots + 1, d_cand, d_ncand, nullptr,
+                               nullptr, stream);
+    orbv_db_detect_reloc_device(db, d_bw, d_bv, d_bn, n, nullptr, nslots + 1, d_cand, d_ncand, nullptr, nullptr, stream);
+    orbv_db_erase(db, slot);
+    orbv_db_clear(db);
+    orbv_db_destroy(db);
+
     // SearchByBoW(KeyFrame*, Frame&)
     std::vector<uint8_t> hasmp(n);
     std::vector<int> n1(1), p1(2), i1(1);
@@ -175,7 +203,7 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     orbm_bow_view b{(const orbx_keypoint*)kps.data(), desc.data(), nullptr, nullptr, n1.data(), p1.data(), i1.data(),
                     n, (int)n1.size()};
     orbm_bow_search(0, ORBM_BOW_KF_F, &a, &b, nullptr, mfNNratio, mbCheckOrientation, match.data(), &nmatches);
-    return dist + nmatches + ngood + nb + nn + nFound;
+    return dist + nmatches + ngood + nb + nn + nFound + ncand;
 }
 
 }  // namespace

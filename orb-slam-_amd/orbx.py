@@ -31,6 +31,7 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle"
 OK, EMPTY, EINVAL, ENOMEM, EDEVICE, ENOSPC = 0, 1, -22, -12, -5, -28
 ORBM_MAX_FEATURES = 16384   # include/orbx.h: keypoints per frame of the matcher searches
 ORBV_MAX_FEATURES = 65536   # include/orbx.h: descriptors per frame of the vocabulary transform
+ORBV_DB_MAX_KEYFRAMES = 65536   # include/orbx.h: KeyFrameDatabase slots between clears
 TOP2, FULL_U16 = 0, 1
 RESIZE_SCALAR, RESIZE_SSE2 = 0, 1              # orbx_set_cv_modes (include/orbx.h)
 BLUR_SCALAR, BLUR_SSE2, BLUR_BITEXACT = 0, 1, 2
@@ -49,6 +50,9 @@ EXPORTED = [
     "orbx_rgbd_stereo", "orbm_frustum_batch_device", "orbm_frustum",
     "orbm_best2_csr_device", "orbm_best2_csr", "orbm_stereo_band", "orbm_stereo_band_device",
     "orbv_load_text", "orbv_create", "orbv_destroy", "orbv_info", "orbv_transform", "orbv_transform_batch_device",
+    "orbv_score", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_batch_device", "orbv_db_erase",
+    "orbv_db_clear", "orbv_db_info", "orbv_db_scores", "orbv_db_detect_loop", "orbv_db_detect_reloc",
+    "orbv_db_detect_loop_device", "orbv_db_detect_reloc_device",
 ]
 BOW_KF_F, BOW_KF_KF, TRIANGULATION = 0, 1, 2
 
@@ -211,6 +215,22 @@ def _load():
     L.orbv_info.argtypes = [vp, i32p, i32p, i32p, i32p, i32p, i32p]
     L.orbv_transform.argtypes = [vp, u8p, C.c_int, C.c_int, i32p, f64p, i32p, i32p, i32p, i32p, i32p]
     L.orbv_transform_batch_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbv_score.argtypes = [C.c_int, i32p, f64p, C.c_int, i32p, f64p, C.c_int, f64p]
+    L.orbv_db_create.argtypes = [vp, C.c_int, C.c_int, P(vp)]
+    L.orbv_db_destroy.argtypes = [vp]
+    L.orbv_db_destroy.restype = None
+    L.orbv_db_add.argtypes = [vp, i32p, f64p, C.c_int, i32p]
+    L.orbv_db_add_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, i32p, vp]
+    L.orbv_db_erase.argtypes = [vp, C.c_int]
+    L.orbv_db_clear.argtypes = [vp]
+    L.orbv_db_info.argtypes = [vp, i32p, i32p, P(C.c_size_t)]
+    L.orbv_db_scores.argtypes = [vp, i32p, f64p, C.c_int, i32p, C.c_int, f64p]
+    L.orbv_db_detect_loop.argtypes = [vp, i32p, f64p, C.c_int, u8p, i32p, C.c_float, i32p, C.c_int, i32p, i32p,
+                                      f32p]
+    L.orbv_db_detect_reloc.argtypes = [vp, i32p, f64p, C.c_int, i32p, i32p, C.c_int, i32p, i32p, f32p]
+    L.orbv_db_detect_loop_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, vp, vp, vp, vp,
+                                             vp]
+    L.orbv_db_detect_reloc_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
     L.orbm_search_by_projection_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int,
                                                    P(ProjParams), vp, vp, vp]
     L.orbm_search_by_projection.argtypes = [C.c_int, vp, u8p, f32p, u8p, C.c_int, vp, u8p, C.c_int, P(ProjParams),
@@ -1051,6 +1071,172 @@ class ORBVocabulary:
                                                _ptr(bv), _ptr(bn), _ptr(fn), _ptr(fp), _ptr(fi), _ptr(fnn),
                                                _stream(stream)))
         return bw, bv, bn, fn, fp, fi, fnn
+
+    @staticmethod
+    def score(b1, b2, scoring=0):
+        """TemplatedVocabulary::score(v1, v2) of two BowVectors, each a (words, weights) pair (L1_NORM only)."""
+        w1, v1 = _bow(b1)
+        w2, v2 = _bow(b2)
+        out = C.c_double(0.0)
+        _check("orbv_score", lib.orbv_score(scoring, _i32p(w1), _f64p(v1), len(w1), _i32p(w2), _f64p(v2), len(w2),
+                                            C.byref(out)))
+        return out.value
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _f64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _bow(b):
+    w = np.ascontiguousarray(b[0], np.int32).reshape(-1)
+    v = np.ascontiguousarray(b[1], np.float64).reshape(-1)
+    if len(w) != len(v):
+        raise ValueError("a BowVector's words and weights differ in length")
+    return w, v
+
+
+class KeyFrameDatabase:
+    """KeyFrameDatabase (src/KeyFrameDatabase.cc) on the vocabulary's device.  Keyframes are slots: add() returns
+    0, 1, ... in add order and every query speaks of keyframes by slot.  BowVectors are (words, weights) pairs as
+    ORBVocabulary.transform returns them."""
+
+    def __init__(self, voc, reserve_keyframes=0, reserve_words=0):
+        self._h = None
+        h = C.c_void_p()
+        _check("orbv_db_create", lib.orbv_db_create(voc._h, reserve_keyframes, reserve_words, C.byref(h)))
+        self._h = h
+        self._voc = voc   # the database reads the vocabulary's device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.orbv_db_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, bow):
+        w, v = _bow(bow)
+        slot = C.c_int(-1)
+        _check("orbv_db_add", lib.orbv_db_add(self._h, _i32p(w), _f64p(v), len(w), C.byref(slot)))
+        return slot.value
+
+    def add_batch_device(self, bow_word, bow_weight, bow_n, nframes=None, stream=None):
+        """Frames 0..nframes-1 of a transform_batch_device result (device tensors); returns their slots."""
+        B = bow_word.shape[0] if nframes is None else int(nframes)
+        slots = np.zeros(max(B, 1), np.int32)
+        _check("orbv_db_add_batch_device",
+               lib.orbv_db_add_batch_device(self._h, _ptr(bow_word), _ptr(bow_weight), _ptr(bow_n), B,
+                                            bow_word.shape[1], _i32p(slots), _stream(stream)))
+        return slots[:B].copy()
+
+    def erase(self, slot):
+        _check("orbv_db_erase", lib.orbv_db_erase(self._h, int(slot)))
+
+    def clear(self):
+        _check("orbv_db_clear", lib.orbv_db_clear(self._h))
+
+    def info(self):
+        """(nslots, nlive, words_stored)"""
+        ns, nl, ws = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        _check("orbv_db_info", lib.orbv_db_info(self._h, C.byref(ns), C.byref(nl), C.byref(ws)))
+        return ns.value, nl.value, ws.value
+
+    def scores(self, bow, slots):
+        """score(bow, slot) as float64 per listed slot (LoopClosing::DetectLoop's reference-score loop)."""
+        w, v = _bow(bow)
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = np.zeros(len(sl), np.float64)
+        _check("orbv_db_scores", lib.orbv_db_scores(self._h, _i32p(w), _f64p(v), len(w), _i32p(sl), len(sl),
+                                                    _f64p(out)))
+        return out
+
+    def _covis(self, covis, ns):
+        if covis is None:
+            return None
+        c = np.ascontiguousarray(covis, np.int32)
+        if c.shape != (ns, 10):
+            raise ValueError("covis must be (nslots, 10)")
+        return c
+
+    def _detect(self, loop, bow, connected, covis, min_score, cap, want_state=True):
+        w, v = _bow(bow)
+        ns = self.info()[0]
+        cv = self._covis(covis, ns)
+        cn = None
+        if connected is not None:
+            cn = np.ascontiguousarray(connected, np.uint8).reshape(-1)
+            if len(cn) != ns:
+                raise ValueError("connected must have nslots entries")
+        cap = ns if cap is None else int(cap)
+        cand = np.zeros(max(cap, 1), np.int32)
+        words = np.zeros(max(ns, 1), np.int32)
+        sc = np.zeros(max(ns, 1), np.float32)
+        nc = C.c_int(0)
+        f32 = sc.ctypes.data_as(C.POINTER(C.c_float)) if want_state else None
+        wp = _i32p(words) if want_state else None
+        cvp = _i32p(cv) if cv is not None else None
+        if loop:
+            rc = lib.orbv_db_detect_loop(self._h, _i32p(w), _f64p(v), len(w), _u8(cn) if cn is not None else None,
+                                         cvp, float(min_score), _i32p(cand), cap, C.byref(nc), wp, f32)
+        else:
+            rc = lib.orbv_db_detect_reloc(self._h, _i32p(w), _f64p(v), len(w), cvp, _i32p(cand), cap, C.byref(nc),
+                                          wp, f32)
+        if rc == ENOSPC:
+            err = OrbxError("orbv_db_detect_loop" if loop else "orbv_db_detect_reloc", rc)
+            err.ncand = nc.value
+            raise err
+        _check("orbv_db_detect_loop" if loop else "orbv_db_detect_reloc", rc)
+        if not want_state:
+            return cand[:nc.value].copy(), None, None
+        return cand[:nc.value].copy(), words[:ns].copy(), sc[:ns].copy()
+
+    def DetectLoopCandidates(self, bow, minScore, connected=None, covis=None, cap=None, want_state=True):
+        """Returns (vpLoopCandidates as slots, mnLoopWords per slot, mLoopScore per slot).  cap: room for the
+        candidates (default: every slot).  want_state=False skips the two per-slot arrays (None, None): the
+        form for a caller that does not know the slot count, e.g. while another thread adds keyframes."""
+        return self._detect(True, bow, connected, covis, minScore, cap, want_state)
+
+    def DetectRelocalizationCandidates(self, bow, covis=None, cap=None, want_state=True):
+        """Returns (vpRelocCandidates as slots, mnRelocWords per slot, mRelocScore per slot)."""
+        return self._detect(False, bow, None, covis, 0.0, cap, want_state)
+
+    def _detect_device(self, loop, q_word, q_weight, q_n, connected, covis, min_score, stream):
+        import torch
+        ns = self.info()[0]
+        dev = q_word.device
+        cand = torch.empty((max(ns, 1),), dtype=torch.int32, device=dev)
+        nc = torch.empty((1,), dtype=torch.int32, device=dev)
+        words = torch.empty((max(ns, 1),), dtype=torch.int32, device=dev)
+        sc = torch.empty((max(ns, 1),), dtype=torch.float32, device=dev)
+        q_cap = q_word.shape[-1]
+        if loop:
+            _check("orbv_db_detect_loop_device",
+                   lib.orbv_db_detect_loop_device(self._h, _ptr(q_word), _ptr(q_weight), _ptr(q_n), q_cap,
+                                                  _ptr(connected), _ptr(covis), float(min_score), ns, _ptr(cand),
+                                                  _ptr(nc), _ptr(words), _ptr(sc), _stream(stream)))
+        else:
+            _check("orbv_db_detect_reloc_device",
+                   lib.orbv_db_detect_reloc_device(self._h, _ptr(q_word), _ptr(q_weight), _ptr(q_n), q_cap,
+                                                   _ptr(covis), ns, _ptr(cand), _ptr(nc), _ptr(words), _ptr(sc),
+                                                   _stream(stream)))
+        return cand, nc, words[:ns], sc[:ns]
+
+    def DetectLoopCandidates_device(self, q_word, q_weight, q_n, minScore, connected=None, covis=None, stream=None):
+        """The query is one frame of a transform batch: q_word / q_weight its (cap,) rows, q_n a 1-element int32
+        tensor; connected (nslots,) uint8 and covis (nslots, 10) int32 device tensors or None.  Returns device
+        tensors (cand[nslots], ncand[1], words[nslots], scores[nslots]); asynchronous on the stream."""
+        return self._detect_device(True, q_word, q_weight, q_n, connected, covis, minScore, stream)
+
+    def DetectRelocalizationCandidates_device(self, q_word, q_weight, q_n, covis=None, stream=None):
+        return self._detect_device(False, q_word, q_weight, q_n, None, covis, 0.0, stream)
 
 
 class BowBatch:
