@@ -572,6 +572,56 @@ orbx_status orbm_frustum(int device, const orbm_map_point* pts, int np, const fl
                          const orbm_pose_params* params, float viewing_cos_limit, orbm_proj_point* out,
                          int* ninview);
 
+/* ---- MapPoint refresh: ComputeDistinctiveDescriptors and UpdateNormalAndDepth ----
+ * src/MapPoint.cc:242-307 and :330-371, which the reference runs for every MapPoint of the KeyFrame concerned
+ * after a KeyFrame insertion, a Fuse and a bundle adjustment (src/LocalMapping.cc:152-153, 442-444, 526-527,
+ * src/Tracking.cc:554-555, 720-721, 1169-1170, src/Optimizer.cc:227, 776, 1042, src/LoopClosing.cc:500, 532,
+ * src/MapPoint.cc:212).  They produce what every projection matcher above reads of an orbm_map_point -- nx, ny,
+ * nz, max_dist, min_dist -- and its GetDescriptor().  One call refreshes np MapPoints in place.
+ *
+ * KeyFrame table: the layout of orbm_search_by_sim3_device (d_kps = mvKeysUn, d_desc = mDescriptors, d_counts,
+ * cap, d_pose[f * 12] = row-major 3x4 Tcw) plus d_kf_bad[f] = pKF->isBad().  MapPoint m's mObservations are
+ * d_obs[d_obs_ptr[m] .. d_obs_ptr[m + 1]) as (KeyFrame slot, feature index), in the order the caller's
+ * std::map<KeyFrame*,size_t> iterates them: that order decides ties between medians and the order of the float
+ * sum, and is never changed.  d_ref[m] = (mpRefKF's slot, mObservations[mpRefKF]).  Of params only nlevels and
+ * scale[] are read (pRefKF->mnScaleLevels, mvScaleFactors).
+ *
+ * ORBM_REFRESH_DESCRIPTOR: among the observations whose KeyFrame is not bad, the descriptor with the least
+ * median Hamming distance to all of them (element (int)(0.5*(N-1)) of its sorted row, its own 0 included; the
+ * first row with the strictly smallest median) goes to d_pdesc[m], and its position in the point's full
+ * observation list, bad KeyFrames counted, to d_best[m].  With no good KeyFrame d_pdesc[m] is left as it was.
+ * ORBM_REFRESH_NORMAL_DEPTH, over all observations, bad KeyFrames included as in the reference: nx, ny, nz = the
+ * mean of (Pos - Ow_i) / |Pos - Ow_i| summed in list order; max_dist = |Pos - Ow_ref| * scale[octave of the
+ * ref keypoint]; min_dist = max_dist / scale[nlevels - 1].  A point on a camera centre gets a NaN normal.
+ *
+ * d_best[m]: >= 0 the winner (only when ORBM_REFRESH_DESCRIPTOR wrote d_pdesc[m]); -1 no descriptor written:
+ * not selected, no good KeyFrame, or the point was skipped -- flags bit 0 clear (mbBad) or an empty list, where
+ * nothing of the point is written; -2 the reference would read out of bounds and nothing of the point is written:
+ * an observation or the ref with kf outside [0, nkf) or idx outside [0, min(d_counts[kf], cap)), the ref keypoint's
+ * octave outside [0, nlevels), a list longer than max_obs or of negative length.  These are checked whatever
+ * `what` selects.  Fields not selected, x, y, z, angle, octave, flags and pad always, and entries at and past np
+ * keep their bits.  max_obs in [1, ORBM_MAX_OBSERVATIONS] is the caller's bound on a list's length and sizes the
+ * LDS.  Asynchronous on `stream`. */
+typedef struct { int32_t kf, idx; } orbm_observation;
+enum { ORBM_REFRESH_DESCRIPTOR = 1, ORBM_REFRESH_NORMAL_DEPTH = 2 };
+#define ORBM_MAX_OBSERVATIONS 1024
+
+orbx_status orbm_refresh_map_points_device(int what, const orbx_keypoint* d_kps, const uint8_t* d_desc,
+                                           const int* d_counts, int nkf, int cap, const float* d_pose,
+                                           const uint8_t* d_kf_bad, const int* d_obs_ptr,
+                                           const orbm_observation* d_obs, const orbm_observation* d_ref, int np,
+                                           int max_obs, const orbm_pose_params* params, orbm_map_point* d_pts,
+                                           uint8_t* d_pdesc, int* d_best, void* stream);
+
+/* Host arrays, on HIP device `device`; pts and pdesc are updated in place.  max_obs is worked out from obs_ptr:
+ * ORBX_EINVAL when a list is longer than ORBM_MAX_OBSERVATIONS or obs_ptr does not ascend from >= 0.
+ * Synchronous. */
+orbx_status orbm_refresh_map_points(int device, int what, const orbx_keypoint* kps, const uint8_t* desc,
+                                    const int* counts, int nkf, int cap, const float* pose, const uint8_t* kf_bad,
+                                    const int* obs_ptr, const orbm_observation* obs, const orbm_observation* ref,
+                                    int np, const orbm_pose_params* params, orbm_map_point* pts, uint8_t* pdesc,
+                                    int* best);
+
 /* ---- DBoW2 vocabulary (TemplatedVocabulary, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h) ----
  * Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:521-528, src/KeyFrame.cc:59-66) call
  * transform(descriptors, mBowVec, mFeatVec, 4); the FeatureVector it produces is the

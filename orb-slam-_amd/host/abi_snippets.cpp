@@ -160,6 +160,26 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
                         n, T1w, (const orbx_keypoint*)kps.data(), desc.data(), mps2.data(), mpdesc2.data(),
                         already2.data(), n, T2w, s12, R12, t12, &P, match12.data(), &nFound, nullptr, nullptr);
 
+    // MapPoint refresh: ComputeDistinctiveDescriptors + UpdateNormalAndDepth over a KeyFrame table
+    int nkf = 3;
+    std::vector<orbx_keypoint> tkps((size_t)nkf * cap);
+    std::vector<uint8_t> tdesc((size_t)nkf * cap * 32), kf_bad(nkf);
+    std::vector<int> tcounts(nkf), obs_ptr(np + 1), best_obs(np);
+    std::vector<float> Tcw((size_t)nkf * 12);
+    std::vector<orbm_observation> obs, ref(np);
+    orbm_refresh_map_points(0, ORBM_REFRESH_DESCRIPTOR | ORBM_REFRESH_NORMAL_DEPTH, tkps.data(), tdesc.data(),
+                            tcounts.data(), nkf, cap, Tcw.data(), kf_bad.data(), obs_ptr.data(), obs.data(), ref.data(),
+                            np, &P, mps.data(), pdesc.data(), best_obs.data());
+    const uint8_t* d_kf_bad = nullptr;
+    const int* d_obs_ptr = nullptr;
+    const orbm_observation *d_obs = nullptr, *d_ref = nullptr;
+    orbm_map_point* d_mps_rw = nullptr;
+    uint8_t* d_pdesc_rw = nullptr;
+    int* d_best = nullptr;
+    int max_obs = 64;
+    orbm_refresh_map_points_device(ORBM_REFRESH_NORMAL_DEPTH, d_kps_un, d_desc, d_counts, nkf, cap, d_Tcw, d_kf_bad,
+                                   d_obs_ptr, d_obs, d_ref, np, max_obs, &P, d_mps_rw, d_pdesc_rw, d_best, stream);
+
     // ComputeBoW
     std::vector<int32_t> bw(n), node(n), ptr(n + 1), idx(n);
     std::vector<double> bv(n);

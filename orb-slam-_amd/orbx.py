@@ -48,6 +48,7 @@ EXPORTED = [
     "orbm_search_by_sim3_device", "orbm_search_by_sim3",
     "orbx_undistort_points", "orbx_image_bounds", "orbx_undistort_batch_device", "orbx_rgbd_stereo_batch_device",
     "orbx_rgbd_stereo", "orbm_frustum_batch_device", "orbm_frustum",
+    "orbm_refresh_map_points_device", "orbm_refresh_map_points",
     "orbm_best2_csr_device", "orbm_best2_csr", "orbm_stereo_band", "orbm_stereo_band_device",
     "orbv_load_text", "orbv_create", "orbv_destroy", "orbv_info", "orbv_transform", "orbv_transform_batch_device",
     "orbv_score", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_batch_device", "orbv_db_erase",
@@ -117,6 +118,11 @@ def frame_grid(bounds):
 MAP_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
                             ("max_dist", "<f4"), ("min_dist", "<f4"), ("angle", "<f4"), ("octave", "<i4"),
                             ("flags", "<i4"), ("pad", "<i4")])
+
+
+OBSERVATION_DTYPE = np.dtype([("kf", "<i4"), ("idx", "<i4")])   # orbm_observation: KeyFrame slot, mObservations[pKF]
+REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
+ORBM_MAX_OBSERVATIONS = 1024   # include/orbx.h: observations of one MapPoint in a refresh
 
 
 class PoseParams(C.Structure):
@@ -256,6 +262,10 @@ def _load():
                                    f32p]
     L.orbm_frustum_batch_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, P(PoseParams), C.c_float, vp, vp, vp]
     L.orbm_frustum.argtypes = [C.c_int, vp, C.c_int, f32p, P(PoseParams), C.c_float, vp, i32p]
+    L.orbm_refresh_map_points_device.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int,
+                                                 C.c_int, P(PoseParams), vp, vp, vp, vp]
+    L.orbm_refresh_map_points.argtypes = [C.c_int, C.c_int, vp, u8p, i32p, C.c_int, C.c_int, f32p, u8p, i32p, vp, vp,
+                                          C.c_int, P(PoseParams), vp, u8p, i32p]
     L.orbm_best2_csr_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     L.orbm_best2_csr.argtypes = [C.c_int, u8p, C.c_int, u8p, C.c_int, i32p, i32p, C.c_int, i32p, i32p, i32p]
     L.orbm_stereo_band.argtypes = [C.c_int, vp, u8p, C.c_int, vp, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_float,
@@ -618,6 +628,56 @@ def frustum(pts, pose, params, viewing_cos_limit=0.5, device=0):
     _check("orbm_frustum", lib.orbm_frustum(device, pp.ctypes.data, len(pp), _f32p(ps), C.byref(prm),
                                             viewing_cos_limit, out.ctypes.data, C.byref(nv)))
     return out[:len(pp)].copy(), nv.value
+
+
+def refresh_map_points_device(what, kps, desc, counts, pose, kf_bad, obs_ptr, obs, ref, max_obs, params, pts, pdesc,
+                              best=None, stream=None):
+    """MapPoint::ComputeDistinctiveDescriptors (what & REFRESH_DESCRIPTOR) and UpdateNormalAndDepth (what &
+    REFRESH_NORMAL_DEPTH) over device tensors, in place.  KeyFrame table as for search_by_sim3_batch_device: kps
+    (B, cap, 7) int32, desc (B, cap, 32) uint8, counts (B,), pose (B, 12) float32 Tcw; kf_bad (B,) uint8 = isBad().
+    obs_ptr (np + 1,) int32 and obs (nobs, 2) int32 = each MapPoint's (KeyFrame slot, feature index) list in the
+    order of its std::map; ref (np, 2) int32 = (mpRefKF's slot, its feature index); max_obs >= the longest list.
+    pts (np, 12) int32 view of MAP_POINT_DTYPE and pdesc (np, 32) uint8 are updated.  Returns best (np,) int32:
+    the winner's position in the list, -1 nothing chosen, -2 invalid input (include/orbx.h)."""
+    import torch
+    n = obs_ptr.shape[0] - 1
+    if best is None:
+        best = torch.empty((max(n, 1),), dtype=torch.int32, device=pts.device)[:n]
+    prm = PoseParams.from_buffer_copy(params)
+    _check("orbm_refresh_map_points_device",
+           lib.orbm_refresh_map_points_device(int(what), _ptr(kps), _ptr(desc), _ptr(counts), kps.shape[0],
+                                              kps.shape[1], _ptr(pose), _ptr(kf_bad), _ptr(obs_ptr), _ptr(obs),
+                                              _ptr(ref), n, int(max_obs), C.byref(prm), _ptr(pts), _ptr(pdesc),
+                                              _ptr(best), _stream(stream)))
+    return best
+
+
+def refresh_map_points(what, kps, desc, counts, pose, kf_bad, obs_ptr, obs, ref, params, pts, pdesc, device=0):
+    """The same on host arrays: kps (B, cap) KEYPOINT_DTYPE, desc (B, cap, 32), counts (B,), pose (B, 12) or
+    (B, 3, 4), kf_bad (B,), obs_ptr (np + 1,), obs / ref OBSERVATION_DTYPE, pts MAP_POINT_DTYPE, pdesc (np, 32).
+    Returns (pts, pdesc, best): refreshed copies and the winners' positions."""
+    k = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+    B, cap = (k.shape[0], k.shape[1]) if k.ndim == 2 else (0, 1)
+    d = np.ascontiguousarray(desc, np.uint8)
+    cn = np.ascontiguousarray(counts, np.int32)
+    po = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(-1))
+    bad = np.ascontiguousarray(kf_bad, np.uint8)
+    op = np.ascontiguousarray(obs_ptr, np.int32)
+    ob = np.ascontiguousarray(obs, OBSERVATION_DTYPE)
+    rf = np.ascontiguousarray(ref, OBSERVATION_DTYPE)
+    n = len(op) - 1
+    p = np.array(pts, MAP_POINT_DTYPE, ndmin=1)
+    pd = np.array(pdesc, np.uint8).reshape(-1, 32)
+    if not (len(cn) == len(bad) == B and len(po) == 12 * B and d.size == 32 * k.size and len(rf) == len(p) ==
+            len(pd) == n and (n == 0 or len(ob) >= op[-1])):
+        raise ValueError("refresh_map_points: array sizes disagree")
+    best = np.full(max(n, 1), -1, np.int32)
+    prm = PoseParams.from_buffer_copy(params)
+    _check("orbm_refresh_map_points",
+           lib.orbm_refresh_map_points(device, int(what), k.ctypes.data, _u8(d), _i32p(cn), B, cap, _f32p(po),
+                                       _u8(bad), _i32p(op), ob.ctypes.data, rf.ctypes.data, n, C.byref(prm),
+                                       p.ctypes.data, _u8(pd), _i32p(best)))
+    return p, pd, best[:n].copy()
 
 
 TIE_FIRST, TIE_LAST = 0, 1
