@@ -622,6 +622,80 @@ orbx_status orbm_refresh_map_points(int device, int what, const orbx_keypoint* k
                                     int np, const orbm_pose_params* params, orbm_map_point* pts, uint8_t* pdesc,
                                     int* best);
 
+/* ---- New MapPoints: the match loop of LocalMapping::CreateNewMapPoints ----
+ * src/LocalMapping.cc:284-450, between SearchForTriangulation (orbm_bow_search_device, ORBM_TRIANGULATION) and the
+ * MapPoint refresh above.  For every vMatchedPairs entry: the parallax of the two rays, a 4x4 cv::SVD triangulation
+ * or KeyFrame::UnprojectStereo (src/KeyFrame.cc:615-631), the depth signs, the chi-square reprojection error (5.991
+ * mono, 7.8 stereo) and the scale consistency test; what passes becomes a MapPoint.  ComputeF12, the baseline test
+ * and ComputeSceneMedianDepth (:244-264) stay with the caller, who fills orbm_triang_params and chooses the pairs.
+ *
+ * KeyFrame table: the layout of orbm_search_by_sim3_device / orbm_refresh_map_points_device (d_kps = mvKeysUn,
+ * d_counts, cap, d_pose[f * 12] = row-major 3x4 Tcw) plus d_kps_raw = mvKeys (NULL = d_kps; UnprojectStereo reads
+ * mvKeys, src/KeyFrame.cc:620) and d_uright / d_depth = mvuRight / mvDepth (both NULL = monocular, all -1).  Pair p:
+ * KF1 = d_pair_a[p] (mpCurrentKeyFrame), KF2 = d_pair_b[p] (the neighbour), d_match[p * match_stride + idx1] = idx2
+ * as orbm_bow_search_device leaves it, match_stride >= cap.  Both KeyFrames share one orbm_pose_params; of it only
+ * fx, fy, cx, cy, bf, b, nlevels and scale[] are read: invfx = 1.0f / fx, mvLevelSigma2[o] = scale[o] * scale[o],
+ * ratioFactor = 1.5f * scale[1].  With shared intrinsics the reference's use of mpCurrentKeyFrame->mbf for
+ * KeyFrame 2 (:406) makes no difference.
+ *
+ * d_status[p * match_stride + idx1], idx1 < cap, one orbm_triang_status each.  A pair whose KeyFrame slot is outside
+ * [0, nkf) gets ORBM_TRI_INVALID in all its cap entries.  Otherwise the range checks come before any indexed read:
+ * idx2 outside [0, min(d_counts[kf2], cap)), a keypoint octave outside [0, nlevels), or a stereo keypoint
+ * (uright >= 0) whose depth is not > 0 (the reference would dereference an empty Mat) give ORBM_TRI_INVALID, and
+ * nothing but the status is written for the entry.  d_x3d[(p * match_stride + idx1) * 3 ..] is written for created
+ * points only; every other entry keeps its bits.
+ *
+ * Compacted outputs: pair p's created points at d_new_*[p * match_stride + k], k < d_nnew[p], in ascending idx1 --
+ * the order of vMatchedIndices and so of mlpRecentAddedMapPoints.  d_new_pts[k]: x, y, z, flags = 3 (not bad,
+ * Observations() > 0), all else 0.  d_new_obs[2k], [2k + 1]: (kf1, idx1) and (kf2, idx2), the KeyFrame with the
+ * smaller d_kf_rank first (d_kf_rank[f] = the position of KeyFrame f in the caller's std::map<KeyFrame*, size_t>
+ * order; NULL = slot order).  With two observations both medians of ComputeDistinctiveDescriptors are 0 and it keeps
+ * the first row, so this order decides the descriptor.  d_new_ref[k] = (kf1, idx1): mpRefKF is the current
+ * KeyFrame.  d_new_idx1[k] = idx1.  Entries at and past d_nnew[p] keep their bits.  These are the d_pts, d_obs and
+ * d_ref of orbm_refresh_map_points_device with d_obs_ptr[k] = 2 * k (one pair: np = d_nnew[p], the arrays offset by
+ * p * match_stride, max_obs = 2); one refresh call finishes the new MapPoints.
+ *
+ * d_mark (NULL = not wanted): [nkf * cap] bytes; every created point stores 1 at d_mark[kf1 * cap + idx1] and
+ * d_mark[kf2 * cap + idx2], nothing else is written.  Hand in the array the views' has_mp point into and the next
+ * neighbour's orbm_bow_search_device on the same stream sees the reference's state.  As in the reference's loop, the
+ * pairs of one current KeyFrame belong in successive calls.  Asynchronous on `stream`. */
+typedef enum {
+    ORBM_TRI_NO_MATCH = 0,         /* d_match < 0, or idx1 at or past the KeyFrame's count */
+    ORBM_TRI_CREATED_SVD = 1,      /* linear triangulation (:321-338) */
+    ORBM_TRI_CREATED_STEREO1 = 2,  /* mpCurrentKeyFrame->UnprojectStereo(idx1) (:342) */
+    ORBM_TRI_CREATED_STEREO2 = 3,  /* pKF2->UnprojectStereo(idx2) (:346) */
+    ORBM_TRI_LOW_PARALLAX = 4,     /* no stereo and very low parallax (:349) */
+    ORBM_TRI_W_ZERO = 5,           /* x3D.at<float>(3)==0 (:333) */
+    ORBM_TRI_Z1 = 6,               /* z1<=0 (:355) */
+    ORBM_TRI_Z2 = 7,               /* z2<=0 (:359) */
+    ORBM_TRI_REPROJ1 = 8,          /* reprojection error in the first KeyFrame (:374, :385) */
+    ORBM_TRI_REPROJ2 = 9,          /* reprojection error in the second KeyFrame (:400, :411) */
+    ORBM_TRI_ZERO_DIST = 10,       /* dist1==0 || dist2==0 (:422) */
+    ORBM_TRI_SCALE = 11,           /* scale consistency (:430) */
+    ORBM_TRI_INVALID = 12          /* the reference would read out of bounds */
+} orbm_triang_status;
+
+orbx_status orbm_triangulate_device(const orbx_keypoint* d_kps, const orbx_keypoint* d_kps_raw, const float* d_uright,
+                                    const float* d_depth, const int* d_counts, int nkf, int cap, const float* d_pose,
+                                    const int* d_kf_rank, const int* d_pair_a, const int* d_pair_b, int npairs,
+                                    const int* d_match, int match_stride, const orbm_pose_params* params, float* d_x3d,
+                                    int* d_status, orbm_map_point* d_new_pts, orbm_observation* d_new_obs,
+                                    orbm_observation* d_new_ref, int* d_new_idx1, int* d_nnew, uint8_t* d_mark,
+                                    void* stream);
+
+/* One pair, host arrays, on HIP device `device`; synchronous.  KeyFrame 1: kps1 (mvKeysUn), kps1_raw (mvKeys; NULL
+ * with kps2_raw NULL = the same), uright1 / depth1 (all four stereo arrays NULL = monocular), n1, T1w (12 floats,
+ * row-major 3x4 Tcw); likewise KeyFrame 2.  match: n1 ints.  KeyFrame 1 counts as slot 0 and KeyFrame 2 as slot 1 in
+ * the observations, and the slot order decides which comes first.  x3d (3 * n1 floats, updated in place), status
+ * (n1) and the compacted arrays (room for n1 points; new_obs 2 * n1) as above; only the first *nnew compacted
+ * entries are written.  mark1 (n1 bytes) and mark2 (n2 bytes), both or neither, are updated in place. */
+orbx_status orbm_triangulate(int device, const orbx_keypoint* kps1, const orbx_keypoint* kps1_raw, const float* uright1,
+                             const float* depth1, int n1, const float* T1w, const orbx_keypoint* kps2,
+                             const orbx_keypoint* kps2_raw, const float* uright2, const float* depth2, int n2,
+                             const float* T2w, const int* match, const orbm_pose_params* params, float* x3d,
+                             int* status, orbm_map_point* new_pts, orbm_observation* new_obs,
+                             orbm_observation* new_ref, int* new_idx1, int* nnew, uint8_t* mark1, uint8_t* mark2);
+
 /* ---- DBoW2 vocabulary (TemplatedVocabulary, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h) ----
  * Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:521-528, src/KeyFrame.cc:59-66) call
  * transform(descriptors, mBowVec, mFeatVec, 4); the FeatureVector it produces is the

@@ -180,6 +180,35 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     orbm_refresh_map_points_device(ORBM_REFRESH_NORMAL_DEPTH, d_kps_un, d_desc, d_counts, nkf, cap, d_Tcw, d_kf_bad,
                                    d_obs_ptr, d_obs, d_ref, np, max_obs, &P, d_mps_rw, d_pdesc_rw, d_best, stream);
 
+    // New MapPoints: the match loop of LocalMapping::CreateNewMapPoints, one neighbour on host arrays
+    std::vector<float> uright(n, -1.0f), depth(n, -1.0f), x3d((size_t)3 * n);
+    std::vector<int> vmatch(n, -1), tri_status(n), new_idx1(n);
+    std::vector<orbm_map_point> new_pts(n);
+    std::vector<orbm_observation> new_obs((size_t)2 * n), new_ref(n);
+    std::vector<uint8_t> has_mp1(n), has_mp2(n);
+    int nnew = 0;
+    orbm_triangulate(0, (const orbx_keypoint*)kps.data(), (const orbx_keypoint*)kps.data(), uright.data(), depth.data(),
+                     n, T1w, (const orbx_keypoint*)kps.data(), (const orbx_keypoint*)kps.data(), uright.data(),
+                     depth.data(), n, T2w, vmatch.data(), &P, x3d.data(), tri_status.data(), new_pts.data(),
+                     new_obs.data(), new_ref.data(), new_idx1.data(), &nnew, has_mp1.data(), has_mp2.data());
+    if (nnew > 0 && tri_status[new_idx1[0]] == ORBM_TRI_CREATED_SVD) new_pts[0].flags = 3;
+    // ... and any number of pairs on the device, emitting the refresh's d_pts / d_obs / d_ref
+    const orbx_keypoint* d_kps_raw = nullptr;
+    const float *d_uright_t = nullptr, *d_depth_t = nullptr;
+    const int *d_rank = nullptr, *d_tri_a = nullptr, *d_tri_b = nullptr, *d_vmatch = nullptr;
+    float* d_x3d = nullptr;
+    int *d_tri_status = nullptr, *d_new_idx1 = nullptr, *d_nnew = nullptr;
+    orbm_map_point* d_new_pts = nullptr;
+    orbm_observation *d_new_obs = nullptr, *d_new_ref = nullptr;
+    uint8_t* d_has_mp = nullptr;
+    int tri_pairs = 20, match_stride = cap;
+    orbm_triangulate_device(d_kps_un, d_kps_raw, d_uright_t, d_depth_t, d_counts, nkf, cap, d_Tcw, d_rank, d_tri_a,
+                            d_tri_b, tri_pairs, d_vmatch, match_stride, &P, d_x3d, d_tri_status, d_new_pts, d_new_obs,
+                            d_new_ref, d_new_idx1, d_nnew, d_has_mp, stream);
+    orbm_refresh_map_points_device(ORBM_REFRESH_DESCRIPTOR | ORBM_REFRESH_NORMAL_DEPTH, d_kps_un, d_desc, d_counts, nkf,
+                                   cap, d_Tcw, d_kf_bad, d_obs_ptr, d_new_obs, d_new_ref, match_stride, 2, &P,
+                                   d_new_pts, d_pdesc_rw, d_best, stream);
+
     // ComputeBoW
     std::vector<int32_t> bw(n), node(n), ptr(n + 1), idx(n);
     std::vector<double> bv(n);

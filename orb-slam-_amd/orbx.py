@@ -48,7 +48,7 @@ EXPORTED = [
     "orbm_search_by_sim3_device", "orbm_search_by_sim3",
     "orbx_undistort_points", "orbx_image_bounds", "orbx_undistort_batch_device", "orbx_rgbd_stereo_batch_device",
     "orbx_rgbd_stereo", "orbm_frustum_batch_device", "orbm_frustum",
-    "orbm_refresh_map_points_device", "orbm_refresh_map_points",
+    "orbm_refresh_map_points_device", "orbm_refresh_map_points", "orbm_triangulate_device", "orbm_triangulate",
     "orbm_best2_csr_device", "orbm_best2_csr", "orbm_stereo_band", "orbm_stereo_band_device",
     "orbv_load_text", "orbv_create", "orbv_destroy", "orbv_info", "orbv_transform", "orbv_transform_batch_device",
     "orbv_score", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_batch_device", "orbv_db_erase",
@@ -266,6 +266,10 @@ def _load():
                                                  C.c_int, P(PoseParams), vp, vp, vp, vp]
     L.orbm_refresh_map_points.argtypes = [C.c_int, C.c_int, vp, u8p, i32p, C.c_int, C.c_int, f32p, u8p, i32p, vp, vp,
                                           C.c_int, P(PoseParams), vp, u8p, i32p]
+    L.orbm_triangulate_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int,
+                                          P(PoseParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_triangulate.argtypes = [C.c_int, vp, vp, f32p, f32p, C.c_int, f32p, vp, vp, f32p, f32p, C.c_int, f32p, i32p,
+                                   P(PoseParams), f32p, i32p, vp, vp, vp, i32p, i32p, u8p, u8p]
     L.orbm_best2_csr_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     L.orbm_best2_csr.argtypes = [C.c_int, u8p, C.c_int, u8p, C.c_int, i32p, i32p, C.c_int, i32p, i32p, i32p]
     L.orbm_stereo_band.argtypes = [C.c_int, vp, u8p, C.c_int, vp, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_float,
@@ -678,6 +682,88 @@ def refresh_map_points(what, kps, desc, counts, pose, kf_bad, obs_ptr, obs, ref,
                                        _u8(bad), _i32p(op), ob.ctypes.data, rf.ctypes.data, n, C.byref(prm),
                                        p.ctypes.data, _u8(pd), _i32p(best)))
     return p, pd, best[:n].copy()
+
+
+# orbm_triang_status (include/orbx.h): what the match loop of CreateNewMapPoints did with a (pair, idx1) entry
+(TRI_NO_MATCH, TRI_CREATED_SVD, TRI_CREATED_STEREO1, TRI_CREATED_STEREO2, TRI_LOW_PARALLAX, TRI_W_ZERO, TRI_Z1, TRI_Z2,
+ TRI_REPROJ1, TRI_REPROJ2, TRI_ZERO_DIST, TRI_SCALE, TRI_INVALID) = range(13)
+
+
+def triangulate_device(kps, counts, pose, pair_a, pair_b, match, params, kps_raw=None, uright=None, depth=None,
+                       kf_rank=None, mark=None, out=None, stream=None):
+    """The match loop of LocalMapping::CreateNewMapPoints over device tensors.  KeyFrame table as for
+    refresh_map_points_device: kps (B, cap, 7) int32 (mvKeysUn), counts (B,), pose (B, 12) float32 Tcw; kps_raw =
+    mvKeys (None = kps), uright / depth (B, cap) float32 (both None = monocular), kf_rank (B,) int32 = the caller's
+    std::map order of the KeyFrames (None = slot order).  pair_a / pair_b (npairs,) int32; match (npairs, stride)
+    int32 = the output of bow_search_batch_device(TRIANGULATION).  mark: (B, cap) uint8 the views' has_mp point
+    into, or None.  out: a dict of preallocated outputs (any subset).  Returns a dict of tensors: x3d (npairs,
+    stride, 3) float32 (written for created points only), status (npairs, stride) int32 (TRI_*), and per pair,
+    compacted in idx1 order, new_pts (npairs, stride, 12) int32 view of MAP_POINT_DTYPE, new_obs (npairs, stride, 2,
+    2), new_ref (npairs, stride, 2), new_idx1 (npairs, stride), nnew (npairs,).  new_pts[p], new_obs[p].view(-1, 2)
+    and new_ref[p] are the pts, obs and ref of refresh_map_points_device with obs_ptr = 2 * arange(nnew[p] + 1)."""
+    import torch
+    B, cap = kps.shape[0], kps.shape[1]
+    npairs, stride = match.shape[0], match.shape[1]
+    out = dict(out or {})
+    dev = kps.device
+    shapes = dict(x3d=((npairs, stride, 3), torch.float32), status=((npairs, stride), torch.int32),
+                  new_pts=((npairs, stride, 12), torch.int32), new_obs=((npairs, stride, 2, 2), torch.int32),
+                  new_ref=((npairs, stride, 2), torch.int32), new_idx1=((npairs, stride), torch.int32),
+                  nnew=((npairs,), torch.int32))
+    for k, (shape, dt) in shapes.items():
+        if out.get(k) is None:
+            out[k] = torch.zeros(shape, dtype=dt, device=dev)
+        elif tuple(out[k].shape) != shape or out[k].dtype != dt or not out[k].is_contiguous():
+            raise ValueError("triangulate_device: out[%r] must be a contiguous %s tensor of shape %s" % (k, dt, shape))
+    prm = PoseParams.from_buffer_copy(params)
+    _check("orbm_triangulate_device",
+           lib.orbm_triangulate_device(_ptr(kps), _ptr(kps_raw), _ptr(uright), _ptr(depth), _ptr(counts), B, cap,
+                                       _ptr(pose), _ptr(kf_rank), _ptr(pair_a), _ptr(pair_b), npairs, _ptr(match),
+                                       stride, C.byref(prm), _ptr(out["x3d"]), _ptr(out["status"]),
+                                       _ptr(out["new_pts"]), _ptr(out["new_obs"]), _ptr(out["new_ref"]),
+                                       _ptr(out["new_idx1"]), _ptr(out["nnew"]), _ptr(mark), _stream(stream)))
+    return out
+
+
+def triangulate(kps1, pose1, kps2, pose2, match, params, kps1_raw=None, kps2_raw=None, uright1=None, depth1=None,
+                uright2=None, depth2=None, mark1=None, mark2=None, x3d=None, device=0):
+    """The same for one pair on host arrays: kps KEYPOINT_DTYPE, pose 3x4 Tcw, match (n1,) int32.  Returns a dict:
+    x3d (n1, 3) (a copy of the x3d argument, or zeros, with the created points written), status (n1,), new_pts
+    MAP_POINT_DTYPE, new_obs (nnew, 2) and new_ref (nnew,) OBSERVATION_DTYPE with KeyFrame 1 as slot 0 and KeyFrame 2
+    as slot 1, new_idx1 (nnew,), nnew, and mark1 / mark2 (updated copies) when given."""
+    k1, k2 = np.ascontiguousarray(kps1, KEYPOINT_DTYPE), np.ascontiguousarray(kps2, KEYPOINT_DTYPE)
+    n1, n2 = len(k1), len(k2)
+    m = np.ascontiguousarray(match, np.int32)
+    if len(m) != n1:
+        raise ValueError("triangulate: match must have one entry per keypoint of KeyFrame 1")
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    kp = lambda a: None if a is None else np.ascontiguousarray(a, KEYPOINT_DTYPE)
+    r1, r2, u1, d1, u2, d2 = kp(kps1_raw), kp(kps2_raw), f32(uright1), f32(depth1), f32(uright2), f32(depth2)
+    t1 = np.ascontiguousarray(np.asarray(pose1, np.float32).reshape(-1)[:12])
+    t2 = np.ascontiguousarray(np.asarray(pose2, np.float32).reshape(-1)[:12])
+    room = max(n1, 1)
+    x = np.zeros((room, 3), np.float32) if x3d is None else np.array(x3d, np.float32).reshape(-1, 3)
+    if len(x) < n1 or any(a is not None and len(a) != n for a, n in ((r1, n1), (u1, n1), (d1, n1), (mark1, n1),
+                                                                      (r2, n2), (u2, n2), (d2, n2), (mark2, n2))):
+        raise ValueError("triangulate: array sizes disagree")
+    status = np.zeros(room, np.int32)
+    pts = np.zeros(room, MAP_POINT_DTYPE)
+    obs, ref = np.zeros((room, 2), OBSERVATION_DTYPE), np.zeros(room, OBSERVATION_DTYPE)
+    idx1 = np.zeros(room, np.int32)
+    nnew = C.c_int(0)
+    mk1 = None if mark1 is None else np.array(mark1, np.uint8)
+    mk2 = None if mark2 is None else np.array(mark2, np.uint8)
+    vp = lambda a: None if a is None else a.ctypes.data
+    fp = lambda a: None if a is None else _f32p(a)
+    prm = PoseParams.from_buffer_copy(params)
+    _check("orbm_triangulate",
+           lib.orbm_triangulate(device, vp(k1), vp(r1), fp(u1), fp(d1), n1, _f32p(t1), vp(k2), vp(r2), fp(u2), fp(d2),
+                                n2, _f32p(t2), _i32p(m), C.byref(prm), _f32p(x), _i32p(status), pts.ctypes.data,
+                                obs.ctypes.data, ref.ctypes.data, _i32p(idx1), C.byref(nnew),
+                                None if mk1 is None else _u8(mk1), None if mk2 is None else _u8(mk2)))
+    k = nnew.value
+    return dict(x3d=x[:n1], status=status[:n1], new_pts=pts[:k].copy(), new_obs=obs[:k].copy(), new_ref=ref[:k].copy(),
+                new_idx1=idx1[:k].copy(), nnew=k, mark1=mk1, mark2=mk2)
 
 
 TIE_FIRST, TIE_LAST = 0, 1
@@ -1340,10 +1426,12 @@ class BowBatch:
         if not isinstance(kps, torch.Tensor):
             kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE).view(np.int32).reshape(-1, 7)
         node, ptr, idx = (np.ascontiguousarray(a, np.int32) for a in s["fv"])
+        # has_mp / u_right may be cuda tensors too (a row of the array triangulate_device marks): used in place
+        host = lambda a, dt: a if isinstance(a, torch.Tensor) else np.ascontiguousarray(a, dt)
         return BowView(self._t(kps, None), self._t(s["desc"], None),
-                       self._t(np.ascontiguousarray(s["has_mp"], np.uint8), None) if s.get("has_mp") is not None
+                       self._t(host(s["has_mp"], np.uint8), None) if s.get("has_mp") is not None
                        else None,
-                       self._t(np.ascontiguousarray(s["u_right"], np.float32), None) if s.get("u_right") is not None
+                       self._t(host(s["u_right"], np.float32), None) if s.get("u_right") is not None
                        else None,
                        self._t(node, None), self._t(ptr, None), self._t(idx if len(idx) else np.zeros(1, np.int32),
                                                                          None),
