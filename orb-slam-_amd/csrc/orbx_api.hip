@@ -1068,6 +1068,17 @@ void stereo_limits(const orbx_handle* h, float bf, float fx, float* maxD, int* r
     *rband = (int)std::ceil(rmax);
 }
 
+// run(scratch) with `bytes` of stream-ordered scratch, freed behind it on the stream; maps the last error
+template <class Run>
+orbx_status with_scratch(size_t bytes, hipStream_t s, Run run)
+{
+    void* scratch = nullptr;
+    if (hipMallocAsync(&scratch, bytes, s) != hipSuccess) return ORBX_ENOMEM;
+    run(scratch);
+    hipFreeAsync(scratch, s);
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+}
+
 bool same_geometry(const orbx_handle* a, const orbx_handle* b)
 {
     if (!a->geom_ok || !b->geom_ok || a->grows != b->grows || a->gcols != b->gcols) return false;
@@ -1173,13 +1184,10 @@ orbx_status orbm_bow_search_device(int mode, const orbm_bow_view* d_view1, const
         return ORBX_EINVAL;
     if (npairs == 0) return ORBX_OK;
     hipStream_t s = (hipStream_t)stream;
-    int* bins = nullptr;
-    if (hipMallocAsync((void**)&bins, sizeof(int) * (size_t)npairs * match_stride, s) != hipSuccess)
-        return ORBX_ENOMEM;
-    launch_bow(mode, d_view1, d_view2, d_tp, npairs, max_nodes1, nnratio, check_ori, d_match, bins, match_stride,
-               d_nmatches, s);
-    hipFreeAsync(bins, s);
-    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+    return with_scratch(sizeof(int) * (size_t)npairs * match_stride, s, [&](void* bins) {
+        launch_bow(mode, d_view1, d_view2, d_tp, npairs, max_nodes1, nnratio, check_ori, d_match, (int*)bins,
+                   match_stride, d_nmatches, s);
+    });
 }
 
 }  // extern "C"
@@ -1281,12 +1289,10 @@ orbx_status orbm_search_by_projection_device(const orbx_keypoint* d_kps, const u
         return ORBX_EINVAL;
     if (nframes == 0) return ORBX_OK;
     hipStream_t s = (hipStream_t)stream;
-    void* scratch = nullptr;
-    if (hipMallocAsync(&scratch, proj_scratch_bytes(nframes, cap, pcap), s) != hipSuccess) return ORBX_ENOMEM;
-    launch_proj(d_kps, d_desc, d_uright, d_claimed, d_counts, nframes, cap, d_pts, d_pdesc, d_npts, pcap, *params,
-                scratch, d_match, d_nmatches, s);
-    hipFreeAsync(scratch, s);
-    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+    return with_scratch(proj_scratch_bytes(nframes, cap, pcap), s, [&](void* scratch) {
+        launch_proj(d_kps, d_desc, d_uright, d_claimed, d_counts, nframes, cap, d_pts, d_pdesc, d_npts, pcap, *params,
+                    scratch, d_match, d_nmatches, s);
+    });
 }
 
 orbx_status orbm_search_by_projection(int device, const orbx_keypoint* kps, const uint8_t* desc, const float* uright,
@@ -1337,12 +1343,10 @@ orbx_status orbm_project_search_device(int mode, const orbx_keypoint* d_kps, con
         return ORBX_EINVAL;
     if (nframes == 0) return ORBX_OK;
     hipStream_t s = (hipStream_t)stream;
-    void* scratch = nullptr;
-    if (hipMallocAsync(&scratch, pose_scratch_bytes(nframes, cap, pcap), s) != hipSuccess) return ORBX_ENOMEM;
-    launch_pose_search(mode, d_kps, d_desc, d_uright, d_claimed, d_counts, nframes, cap, d_pose, d_pts, d_pdesc,
-                       d_npts, pcap, *params, scratch, d_match, d_nmatches, s);
-    hipFreeAsync(scratch, s);
-    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+    return with_scratch(proj_scratch_bytes(nframes, cap, pcap), s, [&](void* scratch) {
+        launch_pose_search(mode, d_kps, d_desc, d_uright, d_claimed, d_counts, nframes, cap, d_pose, d_pts, d_pdesc,
+                           d_npts, pcap, *params, scratch, d_match, d_nmatches, s);
+    });
 }
 
 orbx_status orbm_project_search(int device, int mode, const orbx_keypoint* kps, const uint8_t* desc,
@@ -1407,12 +1411,11 @@ orbx_status orbm_search_by_sim3_device(const orbx_keypoint* d_kps, const uint8_t
         !d_sim3 || !d_already1 || !d_already2 || !d_match12 || !d_nfound)
         return ORBX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    void* scratch = nullptr;
-    if (hipMallocAsync(&scratch, sim3_scratch_bytes(nkf, npairs, cap), s) != hipSuccess) return ORBX_ENOMEM;
-    launch_search_by_sim3(d_kps, d_desc, d_mps, d_mpdesc, d_counts, nkf, cap, d_pose, d_pair_a, d_pair_b, d_sim3,
-                          d_already1, d_already2, npairs, *params, scratch, d_match12, d_nfound, d_match1, d_match2, s);
-    hipFreeAsync(scratch, s);
-    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+    return with_scratch(sim3_scratch_bytes(nkf, npairs, cap), s, [&](void* scratch) {
+        launch_search_by_sim3(d_kps, d_desc, d_mps, d_mpdesc, d_counts, nkf, cap, d_pose, d_pair_a, d_pair_b, d_sim3,
+                              d_already1, d_already2, npairs, *params, scratch, d_match12, d_nfound, d_match1,
+                              d_match2, s);
+    });
 }
 
 orbx_status orbm_search_by_sim3(int device, const orbx_keypoint* kps1, const uint8_t* desc1,

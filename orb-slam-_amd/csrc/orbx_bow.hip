@@ -279,15 +279,8 @@ __global__ __launch_bounds__(256) void k_bow_rot(int mode, const orbm_bow_view* 
             if (BN[i] >= 0) atomicAdd(&s_hist[BN[i]], 1);
         __syncthreads();
         if (tid == 0) {   // ComputeThreeMaxima, src/ORBmatcher.cc:1679-1723
-            int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < kHisto; ++i) {
-                const int s = s_hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
+            int ind1, ind2, ind3;
+            three_maxima(s_hist, ind1, ind2, ind3);
             s_ind[0] = ind1;
             s_ind[1] = ind2;
             s_ind[2] = ind3;

@@ -130,6 +130,27 @@ __device__ __forceinline__ int rot_bin(float a1, float a2)
     return bin;
 }
 
+// ComputeThreeMaxima (src/ORBmatcher.cc:1679-1723): the three fullest bins of hist[kHisto], -1 where a bin
+// is empty or (ind2, ind3) holds less than 0.1 of the fullest
+__device__ __forceinline__ void three_maxima(const int* hist, int& ind1, int& ind2, int& ind3)
+{
+    int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;   // locals: updated through the references they stay in scratch
+    for (int i = 0; i < kHisto; ++i) {
+        const int s = hist[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
+        else if (s > max3) { max3 = s; i3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+    ind1 = i1;
+    ind2 = i2;
+    ind3 = i3;
+}
+
+// FRAME_GRID_COLS / FRAME_GRID_ROWS (include/Frame.h:37-38): the feature grid of the window searches
+constexpr int kFrameGridCols = 64, kFrameGridRows = 48;
+
 // ---- camera pose arithmetic of the pose-projection searches (orbx_proj.hip) and Frame::isInFrustum
 // (orbx_frame.hip): oracle/orbref.c proj_* operation for operation ----
 __device__ __forceinline__ int ps_x86_int(double v)   // cvttsd2si: NaN / out of range -> INT_MIN

@@ -173,7 +173,7 @@ void launch_ingest(const uint8_t* src, int batch, int rows, int cols, int channe
 void launch_depth(const void* src, int depth_type, int batch, int rows, int cols, size_t sstep, size_t sfs,
                   float factor, float* dst, size_t dstep, size_t dfs, hipStream_t s);
 
-size_t pose_scratch_bytes(int nframes, int cap, int pcap);
+// scratch: proj_scratch_bytes
 void launch_pose_search(int mode, const orbx_keypoint* kps, const uint8_t* desc, const float* uright,
                         const uint8_t* claimed, const int* counts, int nframes, int cap, const float* pose,
                         const orbm_map_point* pts, const uint8_t* pdesc, const int* npts, int pcap,

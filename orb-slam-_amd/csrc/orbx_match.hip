@@ -211,10 +211,9 @@ void launch_allpairs_full(const uint8_t* q, int nq, const uint8_t* t, int nt, ui
 //               the step unless the best is within the ratio of it — then the
 //               wave re-enumerates the window (k_si_build's walk) and scans.
 // ---------------------------------------------------------------------------
-constexpr int kGridCols = 64, kGridRows = 48;
 constexpr int SI_BUILD_NT = 256;
 constexpr int SI_TOPK = 4;
-constexpr int kSiCells = kGridCols * kGridRows;
+constexpr int kSiCells = kFrameGridCols * kFrameGridRows;
 constexpr int kSiRankMax = 4096;   // k_si_grid: rank sort up to this many level-0 keypoints, counting sort above
 
 __host__ __device__ inline size_t si_grid_smem(int cap)
@@ -257,8 +256,8 @@ __global__ __launch_bounds__(256) void k_si_grid(const orbx_keypoint* __restrict
             l0 = true;
             const int px = (int)roundf((k[i].x - G.min_x) * G.grid_w_inv);
             const int py = (int)roundf((k[i].y - G.min_y) * G.grid_h_inv);
-            if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows)   // PosInGrid
-                key = ((uint32_t)(px * kGridRows + py) << 16) | (uint32_t)i;
+            if (px >= 0 && px < kFrameGridCols && py >= 0 && py < kFrameGridRows)   // PosInGrid
+                key = ((uint32_t)(px * kFrameGridRows + py) << 16) | (uint32_t)i;
         }
         keys[i] = key;
         const unsigned long long b0 = __ballot(l0), bg = __ballot(key != 0xFFFFFFFFu);
@@ -354,8 +353,8 @@ struct SiWindow {
 __device__ __forceinline__ void si_colstart(const uint32_t* keys, int ng, int* colstart, int tid, int nt)
 {
     for (int g = tid; g <= ng; g += nt) {
-        const int cp = g > 0 ? (int)(keys[g - 1] >> 16) / kGridRows : -1;
-        const int cc = g < ng ? (int)(keys[g] >> 16) / kGridRows : kGridCols;
+        const int cp = g > 0 ? (int)(keys[g - 1] >> 16) / kFrameGridRows : -1;
+        const int cc = g < ng ? (int)(keys[g] >> 16) / kFrameGridRows : kFrameGridCols;
         for (int c = cp + 1; c <= cc; ++c) colstart[c] = g;
     }
 }
@@ -369,17 +368,17 @@ __device__ __forceinline__ SiWindow si_window(const uint32_t* keys, int ng, floa
     w.y = y;
     w.r = r;
     const int cx0 = max(0, (int)floorf((x - G.min_x - r) * G.grid_w_inv));
-    const int cx1 = min(kGridCols - 1, (int)ceilf((x - G.min_x + r) * G.grid_w_inv));
+    const int cx1 = min(kFrameGridCols - 1, (int)ceilf((x - G.min_x + r) * G.grid_w_inv));
     w.cy0 = max(0, (int)floorf((y - G.min_y - r) * G.grid_h_inv));
-    w.cy1 = min(kGridRows - 1, (int)ceilf((y - G.min_y + r) * G.grid_h_inv));
+    w.cy1 = min(kFrameGridRows - 1, (int)ceilf((y - G.min_y + r) * G.grid_h_inv));
     w.lo = w.hi = 0;
-    if (cx0 < kGridCols && cx1 >= 0 && w.cy0 < kGridRows && w.cy1 >= 0) {
+    if (cx0 < kFrameGridCols && cx1 >= 0 && w.cy0 < kFrameGridRows && w.cy1 >= 0) {
         if (colstart) {   // two independent table reads instead of two binary searches
             w.lo = colstart[cx0];
             w.hi = colstart[cx1 + 1];
         } else {
-            w.lo = lower_bound_u32(keys, ng, (uint32_t)(cx0 * kGridRows) << 16);
-            w.hi = lower_bound_u32(keys, ng, (uint32_t)((cx1 + 1) * kGridRows) << 16);
+            w.lo = lower_bound_u32(keys, ng, (uint32_t)(cx0 * kFrameGridRows) << 16);
+            w.hi = lower_bound_u32(keys, ng, (uint32_t)((cx1 + 1) * kFrameGridRows) << 16);
         }
     }
     return w;
@@ -390,7 +389,7 @@ __device__ __forceinline__ bool si_in_window(const uint32_t* keys, const float2*
 {
     if (g >= w.hi) return false;
     const uint32_t key = keys[g];
-    const int iy = (int)(key >> 16) % kGridRows;
+    const int iy = (int)(key >> 16) % kFrameGridRows;
     if (iy < w.cy0 || iy > w.cy1) return false;
     const float2 p = xy[g];
     i2 = (int)(key & 0xFFFF);
@@ -418,7 +417,7 @@ __global__ __launch_bounds__(SI_BUILD_NT) void k_si_build(const orbx_keypoint* _
     const int fa = pa[pair], fb = pb[pair];
     const int n10 = gn[2 * fa], ng = gn[2 * fb + 1];
     const uint8_t* d2 = desc + (size_t)fb * cap * 32;
-    __shared__ int colstart[kGridCols + 1];
+    __shared__ int colstart[kFrameGridCols + 1];
     // the window scans read F2's grid keys, positions and descriptors once per candidate per query: in LDS
     // when they fit (one L2 round trip per candidate otherwise dominated the kernel)
     const bool staged = ng <= kSiBuildLds;   // block-uniform

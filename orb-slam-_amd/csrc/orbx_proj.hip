@@ -1,18 +1,30 @@
-// gfx950 kernels of ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>, th)
-// (src/ORBmatcher.cc:45-129), the local-map search of Tracking::SearchLocalPoints,
-// over Frame::GetFeaturesInArea (src/Frame.cc:410-495).  SURVEY.md §8f row 3.
+// gfx950 kernels of the matchers that project MapPoints into a frame and search a window of its
+// 64x48 grid in GetFeaturesInArea order (src/Frame.cc:410-495, src/KeyFrame.cc:569-608).  SURVEY.md §8f row 3.
+//   LocalMapSearch   SearchByProjection(Frame&, vector<MapPoint*>, th) (src/ORBmatcher.cc:45-129), the
+//                    local-map search of Tracking::SearchLocalPoints
+//   PoseSearch<MODE> SearchByProjection(CurrentFrame, LastFrame) (:1396-1538), SearchByProjection(CurrentFrame,
+//                    pKF, sAlreadyFound) (:1540-1667), SearchByProjection(pKF, Scw, ...) (:290-403),
+//                    Fuse(pKF, ...) (:893-1043), Fuse(pKF, Scw, ...) (:1045-1168)
+//   Sim3Search       SearchBySim3 (:1170-1394), with kernels of its own at the end of the file
+// A search is a policy struct: its point and parameter types, the projection of a point to a window, the
+// extra candidate test, the fields of a list entry, the accept test and which matches claim a feature.
+// Every search runs the same three stages:
 //
 // J1 k_pj_grid     one workgroup per frame: (cell, feature) keys of AssignFeaturesToGrid
 //                  sorted in LDS, so a window's columns are one key range and the keys
 //                  run in GetFeaturesInArea's visiting order (ix, then iy, then insertion)
-// J2 k_pj_points   one lane per MapPoint: the reference's sequential scan over its window,
-//                  against the frame's claims on entry, kept as the first kTop candidates in
-//                  (distance, visiting position) order -- best and second are the first two
-// J3 k_pj_resolve  one wave per frame replays the MapPoints in order, 64 at a time
+// J2 k_points<S>   kSub lanes per MapPoint: project it (S::project), then the reference's sequential scan
+//                  over its window against the frame's claims on entry, kept as the first kTop candidates
+//                  in (distance, visiting position) order -- best and second are the first two.  The Fuse
+//                  overloads claim nothing during the search: they keep the first minimum and finish here.
+// J3 k_resolve<S>  one wave per frame replays the MapPoints in order, 64 at a time
 //                  (replay_chunks): each takes the first unclaimed entries of its list; the
 //                  lanes before the first collision with an earlier lane's claim commit
 //                  together; a MapPoint whose list ran out searches its window again.
-//                  Assignments and claims live in LDS.
+//                  Assignments and claims live in LDS.  Then, for the searches that check rotation,
+//                  ComputeThreeMaxima over per-feature bin masks.
+// Float arithmetic is oracle/orbref.c proj_* operation for operation (no contraction in this
+// file; the reference's GCC -march=native FMAs are explicit).
 #include <hip/hip_runtime.h>
 
 #include "orbx_device.hpp"
@@ -20,13 +32,11 @@
 
 namespace orbx {
 
-constexpr int kPjCols = 64, kPjRows = 48;   // FRAME_GRID_COLS / ROWS (include/Frame.h:37-38)
-
 // J1 as a stable counting sort over the 3072 cells: per-cell counts by LDS atomics (the
 // arrival slot is unordered), an exclusive scan, a scatter, then each feature's stable rank
 // = the number of lower indices in its own cell segment (a few entries).  Keys are
 // cell << 16 | index in ascending order, i.e. (cell, insertion) order.
-constexpr int kPjCells = kPjCols * kPjRows;
+constexpr int kPjCells = kFrameGridCols * kFrameGridRows;
 
 // per frame: cap keys, then the kPjCells + 1 cell offsets (cell c = keys [off[c], off[c + 1]))
 __host__ __device__ inline size_t pj_grid_stride(int cap) { return (size_t)cap + kPjCells + 4; }
@@ -35,7 +45,7 @@ __host__ __device__ inline size_t pj_grid_smem(int cap) { return (size_t)4 * (kP
 
 __global__ __launch_bounds__(256) void k_pj_grid(const orbx_keypoint* __restrict__ kps, const int* __restrict__ counts,
                                                  int cap, float min_x, float min_y, float grid_w_inv,
-                                                 float grid_h_inv, uint32_t* __restrict__ gkeys, int* __restrict__ gn)
+                                                 float grid_h_inv, uint32_t* __restrict__ gkeys)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_grid[];
     __shared__ uint32_t s_wsum[4];
@@ -52,8 +62,8 @@ __global__ __launch_bounds__(256) void k_pj_grid(const orbx_keypoint* __restrict
         const int px = (int)roundf((k[i].x - min_x) * grid_w_inv);
         const int py = (int)roundf((k[i].y - min_y) * grid_h_inv);
         uint16_t cc = 0xFFFF;
-        if (px >= 0 && px < kPjCols && py >= 0 && py < kPjRows) {
-            cc = (uint16_t)(px * kPjRows + py);
+        if (px >= 0 && px < kFrameGridCols && py >= 0 && py < kFrameGridRows) {
+            cc = (uint16_t)(px * kFrameGridRows + py);
             pos[i] = (uint16_t)atomicAdd(&start[cc], 1u);
         }
         code[i] = cc;
@@ -96,74 +106,121 @@ __global__ __launch_bounds__(256) void k_pj_grid(const orbx_keypoint* __restrict
         for (int j = s0; j < s1; ++j) r += tmp[j] < i;
         out[s0 + r] = (uint32_t)cc << 16 | (uint32_t)i;
     }
-    if (tid == 0) gn[f] = (int)start[kPjCells];
 }
 
-void launch_pj_grid(const orbx_keypoint* kps, const int* counts, int nframes, int cap, float min_x, float min_y,
-                    float grid_w_inv, float grid_h_inv, uint32_t* gkeys, int* gn, hipStream_t s)
+// The stream-ordered scratch of one call: the sorted grids of its frames, then (16-byte aligned) what the
+// search keeps between its kernels -- the J2 lists, or SearchBySim3's vnMatch1 | vnMatch2.
+struct GridScratch {
+    uint32_t* gkeys;
+    void* tail;
+    size_t bytes;
+    GridScratch(void* base, int nframes, int cap, size_t tail_bytes)
+    {
+        const size_t keys = ((size_t)nframes * pj_grid_stride(cap) * 4 + 15) & ~(size_t)15;
+        gkeys = (uint32_t*)base;
+        tail = (uint8_t*)base + keys;
+        bytes = keys + tail_bytes;
+    }
+};
+
+template <class Params>
+static void launch_pj_grid(const orbx_keypoint* kps, const int* counts, int nframes, int cap, const Params& P,
+                           uint32_t* gkeys, hipStream_t s)
 {
     const size_t sm = pj_grid_smem(cap);
     hipFuncSetAttribute((const void*)k_pj_grid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    hipLaunchKernelGGL(k_pj_grid, dim3(nframes), dim3(256), sm, s, kps, counts, cap, min_x, min_y, grid_w_inv,
-                       grid_h_inv, gkeys, gn);
+    hipLaunchKernelGGL(k_pj_grid, dim3(nframes), dim3(256), sm, s, kps, counts, cap, P.min_x, P.min_y, P.grid_w_inv,
+                       P.grid_h_inv, gkeys);
 }
 
-// GetFeaturesInArea(x, y, r * scale[level], level - 1, level) window of one MapPoint
-struct PjWindow {
-    int lo, hi, cx0, cx1, cy0, cy1, minLevel, maxLevel;
-    float x, y, rr, rs;   // rr = window radius; rs = r * scale[level] for the stereo test
-    bool ok;
+// One frame of the batch as a search reads it: sorted grid, keypoints, right coordinates and claims on entry
+// (both null in SearchBySim3, which reads neither), descriptors
+struct FrameView {
+    const uint32_t* keys;
+    const orbx_keypoint* K;
+    const float* U;
+    const uint8_t* C;
+    const uint8_t* D;
+    int cap;
 };
 
-__device__ __forceinline__ PjWindow pj_window(const orbm_proj_point& M, const orbm_proj_params& P,
-                                              const uint32_t* keys, int cap)
+__device__ __forceinline__ FrameView frame_view(const orbx_keypoint* kps, const uint8_t* desc, const float* uright,
+                                                const uint8_t* claimed, const uint32_t* gkeys, int f, int cap)
 {
-    PjWindow w;
-    w.ok = false;
-    w.lo = w.hi = 0;
-    const int level = M.level;
-    if (level < 0 || level >= 16) return w;       // outside mvScaleFactors: UB in the reference
-    float r = M.view_cos > 0.998 ? 2.5f : 4.0f;   // RadiusByViewingCos, src/ORBmatcher.cc:130-136
-    if (P.th != 1.0f) r *= P.th;
-    w.rr = r * P.scale[level];
-    w.rs = r * P.scale[level];
-    w.x = M.proj_x;
-    w.y = M.proj_y;
-    w.minLevel = level - 1;
-    w.maxLevel = level;
-    const int cx0 = max(0, (int)floorf((w.x - P.min_x - w.rr) * P.grid_w_inv));
-    if (cx0 >= kPjCols) return w;
-    const int cx1 = min(kPjCols - 1, (int)ceilf((w.x - P.min_x + w.rr) * P.grid_w_inv));
-    if (cx1 < 0) return w;
-    w.cy0 = max(0, (int)floorf((w.y - P.min_y - w.rr) * P.grid_h_inv));
-    if (w.cy0 >= kPjRows) return w;
-    w.cy1 = min(kPjRows - 1, (int)ceilf((w.y - P.min_y + w.rr) * P.grid_h_inv));
-    if (w.cy1 < 0) return w;
-    w.cx0 = cx0;
-    w.cx1 = cx1;
-    w.lo = (int)keys[cap + cx0 * kPjRows];
-    w.hi = (int)keys[cap + (cx1 + 1) * kPjRows];
-    w.ok = true;
-    return w;
+    const size_t o = (size_t)f * cap;
+    return FrameView{gkeys + (size_t)f * pj_grid_stride(cap), kps + o, uright + o, claimed + o, desc + o * 32, cap};
 }
 
-// candidate at key position p: the feature index if it is in the window (and not claimed,
-// and passes the stereo test), else -1
-__device__ __forceinline__ int pj_candidate(const PjWindow& w, const orbm_proj_point& M, const uint32_t* keys,
-                                            int p, const orbx_keypoint* kps, const float* uright)
+// GetFeaturesInArea(u, v, r, minLevel, maxLevel) of one MapPoint: S::project fills the first line,
+// proj_window the cell box and the key range [lo, hi) of its columns
+struct ProjWindow {
+    float u, v, r, ur;   // ur: the MapPoint's right coordinate, for the stereo tests
+    int minLevel, maxLevel, cx0, cx1, cy0, cy1, lo, hi;
+};
+
+// The float -> int conversion of the cell bounds.  The two differ on NaN and out-of-range values, and each
+// search keeps the one of its reference code: oracle/orbref.c:1546-1551 (local map), :1786-1795 (pose, Sim3).
+struct CastInt {
+    static __device__ __forceinline__ int of(float v) { return (int)v; }
+};
+struct X86Int {
+    static __device__ __forceinline__ int of(float v) { return ps_x86_int(v); }
+};
+
+// false where GetFeaturesInArea returns no feature
+template <class ToInt, class Params>
+__device__ __forceinline__ bool proj_window(ProjWindow& w, const Params& P, const uint32_t* keys, int cap)
 {
-    const uint32_t key = keys[p];
-    const int iy = (int)(key >> 16) % kPjRows;
+    w.lo = w.hi = 0;
+    const int cx0 = max(0, ToInt::of(floorf((w.u - P.min_x - w.r) * P.grid_w_inv)));
+    if (cx0 >= kFrameGridCols) return false;
+    const int cx1 = min(kFrameGridCols - 1, ToInt::of(ceilf((w.u - P.min_x + w.r) * P.grid_w_inv)));
+    if (cx1 < 0) return false;
+    w.cy0 = max(0, ToInt::of(floorf((w.v - P.min_y - w.r) * P.grid_h_inv)));
+    if (w.cy0 >= kFrameGridRows) return false;
+    w.cy1 = min(kFrameGridRows - 1, ToInt::of(ceilf((w.v - P.min_y + w.r) * P.grid_h_inv)));
+    if (w.cy1 < 0) return false;
+    w.cx0 = cx0;
+    w.cx1 = cx1;
+    w.lo = (int)keys[cap + cx0 * kFrameGridRows];
+    w.hi = (int)keys[cap + (cx1 + 1) * kFrameGridRows];
+    return true;
+}
+
+// what a search tests after the shared row, level and box filter
+enum { kNoExtra, kStereoExtra, kChi2Extra };
+
+// candidate at key position p: the feature index if it is in the window and passes the search's extra
+// test, else -1
+template <class S>
+__device__ __forceinline__ int window_candidate(const ProjWindow& w, const FrameView& F, int p,
+                                                const typename S::Params& P)
+{
+    const uint32_t key = F.keys[p];
+    const int iy = (int)(key >> 16) % kFrameGridRows;
     if (iy < w.cy0 || iy > w.cy1) return -1;
     const int idx = (int)(key & 0xFFFF);
-    const orbx_keypoint kp = kps[idx];
-    if (kp.octave < w.minLevel) return -1;   // bCheckLevels is true for level >= 0
+    const orbx_keypoint kp = F.K[idx];
+    if (kp.octave < w.minLevel) return -1;
     if (w.maxLevel >= 0 && kp.octave > w.maxLevel) return -1;
-    const float distx = kp.x - w.x, disty = kp.y - w.y;
-    if (!(fabsf(distx) < w.rr && fabsf(disty) < w.rr)) return -1;
-    if (uright[idx] > 0) {   // src/ORBmatcher.cc:86-91
-        const float er = fabsf(M.proj_xr - uright[idx]);
-        if (er > w.rs) return -1;
+    const float distx = kp.x - w.u, disty = kp.y - w.v;
+    if (!(fabsf(distx) < w.r && fabsf(disty) < w.r)) return -1;
+    if constexpr (S::kExtra == kStereoExtra) {   // :86-91, :1475-1481
+        const float ur = F.U[idx];
+        if (ur > 0 && fabsf(w.ur - ur) > w.r) return -1;
+    }
+    if constexpr (S::kExtra == kChi2Extra) {   // :982-1006
+        const float ur = F.U[idx];
+        const float ex = w.u - kp.x, ey = w.v - kp.y;
+        const float is2 = P.inv_sigma2[kp.octave & 15];
+        if (ur >= 0) {
+            const float er = w.ur - ur;
+            const float e2 = __builtin_fmaf(er, er, __builtin_fmaf(ex, ex, ey * ey));
+            if ((double)(e2 * is2) > 7.8) return -1;
+        } else {
+            const float e2 = __builtin_fmaf(ex, ex, ey * ey);
+            if ((double)(e2 * is2) > 5.99) return -1;
+        }
     }
     return idx;
 }
@@ -278,66 +335,64 @@ struct TopResult {
     int n;        // candidates in the window (not claimed on entry), saturating
     int accept;   // the reference's accept test on the J2 best (and second)
 };
-using PjResult = TopResult;
 
-__device__ __forceinline__ bool pj_accept(int bestDist, int bestLevel, int bestDist2, int bestLevel2, float nnratio)
+// a candidate as (distance, visiting position, index): the minimum is the first minimum of the sequential scan
+__device__ __forceinline__ unsigned long long first_key(int dist, int p, int idx)
 {
-    if (!(bestDist <= 100)) return false;   // TH_HIGH
-    if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) return false;
-    return true;
+    return (unsigned long long)dist << 32 | (unsigned long long)p << 16 | (unsigned)idx;
 }
 
-__global__ __launch_bounds__(256) void k_pj_points(const orbx_keypoint* __restrict__ kps,
-                                                   const uint8_t* __restrict__ desc, const float* __restrict__ uright,
-                                                   const uint8_t* __restrict__ claimed, int cap,
-                                                   const orbm_proj_point* __restrict__ pts,
-                                                   const uint8_t* __restrict__ pdesc, const int* __restrict__ npts,
-                                                   int pcap, orbm_proj_params P, const uint32_t* __restrict__ gkeys,
-                                                   const int* __restrict__ gn, PjResult* __restrict__ res)
+// Sub-lane `sub` of a MapPoint's kSub lanes walks the window's columns in GetFeaturesInArea order (rows
+// cy0..cy1 only): visit(position, index, distance) for every candidate that passes the search's tests and,
+// in a claiming search, is not claimed on entry.  q0 | q1 is the MapPoint's descriptor.
+template <class S, class Visit>
+__device__ __forceinline__ void walk_window(const ProjWindow& w, const FrameView& F, int sub, const uint4& q0,
+                                            const uint4& q1, const typename S::Params& P, Visit visit)
 {
-    const int f = blockIdx.y, m = blockIdx.x * (256 / kSub) + threadIdx.x / kSub, sub = threadIdx.x % kSub;
-    if (m >= min(npts[f], pcap)) return;   // uniform over the kSub lanes of a MapPoint
-    const size_t mo = (size_t)f * pcap + m;
-    TopK64 T64;
-    T64.n = 0;
-#pragma unroll
-    for (int k = 0; k < kTop; ++k) T64.e[k] = 0ull;
-    int accept = 0;
-    const orbm_proj_point M = pts[mo];
-    bool scanned = false;
-    if (M.flags & 1) {
-        const uint32_t* keys = gkeys + (size_t)f * pj_grid_stride(cap);
-        const PjWindow w = pj_window(M, P, keys, cap);
-        if (w.ok) {
-            scanned = true;
-            const orbx_keypoint* K = kps + (size_t)f * cap;
-            const float* U = uright + (size_t)f * cap;
-            const uint8_t* C = claimed + (size_t)f * cap;
-            const uint4* qd = reinterpret_cast<const uint4*>(pdesc + mo * 32);
-            const uint4 q0 = qd[0], q1 = qd[1];
-            for (int cx = w.cx0; cx <= w.cx1; ++cx) {   // src/ORBmatcher.cc:78-113, visiting order
-                const int a = (int)keys[cap + cx * kPjRows + w.cy0], b = (int)keys[cap + cx * kPjRows + w.cy1 + 1];
-                for (int p = a + sub; p < b; p += kSub) {
-                    const int idx = pj_candidate(w, M, keys, p, K, U);
-                    if (idx < 0 || C[idx]) continue;
-                    const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)f * cap + idx) * 32);
-                    top64_insert(T64, top_key(top_entry(ham256(q0, q1, d[0], d[1]), 0, K[idx].octave, idx), p));
-                }
-            }
+    for (int cx = w.cx0; cx <= w.cx1; ++cx) {
+        const int a = (int)F.keys[F.cap + cx * kFrameGridRows + w.cy0], b = (int)F.keys[F.cap + cx * kFrameGridRows + w.cy1 + 1];
+        for (int p = a + sub; p < b; p += kSub) {
+            const int idx = window_candidate<S>(w, F, p, P);
+            if (idx < 0 || (S::kClaims && F.C[idx])) continue;
+            const uint4* d = reinterpret_cast<const uint4*>(F.D + (size_t)idx * 32);
+            visit(p, idx, ham256(q0, q1, d[0], d[1]));
         }
     }
-    const TopK T = top_merge(T64);   // whole group: `scanned` is uniform over it
-    if (sub != 0) return;
-    // the scan's best / second are the first two entries (multiset top two, first wins ties)
-    if (scanned && T.n > 0)
-        accept = pj_accept(top_dist(T.e[0]), top_oct(T.e[0]), T.n > 1 ? top_dist(T.e[1]) : 256,
-                           T.n > 1 ? top_oct(T.e[1]) : -1, P.nnratio);
-    PjResult R;
-#pragma unroll
-    for (int k = 0; k < kTop; ++k) R.e[k] = T.e[k];
-    R.n = T.n;
-    R.accept = accept;
-    res[mo] = R;
+}
+
+// One wave searches the window again against the claims on entry and those made in this call: b1 = the
+// first minimum as first_key packs it and, where the accept test needs it (S::kSecond), b2 = the first
+// minimum of the rest -- the sequential scan's best and second.  ~0 = none.
+template <class S>
+__device__ __forceinline__ void rescan_window(const ProjWindow& w, const FrameView& F, const uint8_t* taken,
+                                              const uint4& q0, const uint4& q1, const typename S::Params& P,
+                                              unsigned long long& b1, unsigned long long& b2)
+{
+    const int lane = threadIdx.x;
+    b1 = b2 = ~0ull;
+    for (int p0 = w.lo; p0 < w.hi; p0 += 64) {
+        const int p = p0 + lane;
+        unsigned long long key = ~0ull;
+        if (p < w.hi) {
+            const int idx = window_candidate<S>(w, F, p, P);
+            if (idx >= 0 && !F.C[idx] && !taken[idx]) {
+                const uint4* d = reinterpret_cast<const uint4*>(F.D + (size_t)idx * 32);
+                key = first_key(ham256(q0, q1, d[0], d[1]), p, idx);
+            }
+        }
+        const unsigned long long c1 = wave_min_shfl(key);
+        if constexpr (S::kSecond) {   // merge: the multiset top two by (dist, position)
+            const unsigned long long c2 = wave_min_shfl(key == c1 ? ~0ull : key);
+            if (c1 < b1) {
+                b2 = min(b1, c2);
+                b1 = c1;
+            } else {
+                b2 = min(b2, c1);
+            }
+        } else {
+            b1 = c1 < b1 ? c1 : b1;
+        }
+    }
 }
 
 // ---- chunk-parallel, in-order replay of the reference's greedy loop (both searches) ----
@@ -479,125 +534,48 @@ __device__ __forceinline__ int replay_chunks(int n, int np, const TopResult* __r
     return count;
 }
 
-template <bool kBig>
-__global__ __launch_bounds__(64) void k_pj_resolve(const orbx_keypoint* __restrict__ kps,
-                                                   const uint8_t* __restrict__ desc, const float* __restrict__ uright,
-                                                   const uint8_t* __restrict__ claimed, const int* __restrict__ counts,
-                                                   int cap, const orbm_proj_point* __restrict__ pts,
-                                                   const uint8_t* __restrict__ pdesc, const int* __restrict__ npts,
-                                                   int pcap, orbm_proj_params P, const uint32_t* __restrict__ gkeys,
-                                                   const int* __restrict__ gn, const PjResult* __restrict__ res,
-                                                   int* __restrict__ match, int* __restrict__ nmatches)
-{
-    const int f = blockIdx.x, lane = threadIdx.x;
-    const int n = min(counts[f], cap), np = min(npts[f], pcap);
-    int* Mo = match + (size_t)f * cap;
-    const ReplayLds S = replay_lds<kBig>(cap, Mo);
-    const uint32_t* keys = gkeys + (size_t)f * pj_grid_stride(cap);
-    const orbx_keypoint* K = kps + (size_t)f * cap;
-    const float* U = uright + (size_t)f * cap;
-    const uint8_t* C = claimed + (size_t)f * cap;
-    const orbm_proj_point* Pf = pts + (size_t)f * pcap;
-    auto obs_of = [&](int m) { return (Pf[m].flags & 2) ? 1 : 0; };
-    auto accept_of = [&](uint32_t c1, bool has2, uint32_t c2) {
-        return pj_accept(top_dist(c1), top_oct(c1), has2 ? top_dist(c2) : 256, has2 ? top_oct(c2) : -1, P.nnratio);
-    };
-    // search again against the current claims: best = first min of (dist, position), second = first
-    // min of the rest (the sequential scan's result)
-    auto rescan = [&](int m, const uint8_t* taken) {
-        const orbm_proj_point Mp = Pf[m];
-        const PjWindow w = pj_window(Mp, P, keys, cap);
-        const uint4* qd = reinterpret_cast<const uint4*>(pdesc + ((size_t)f * pcap + m) * 32);
-        const uint4 q0 = qd[0], q1 = qd[1];
-        unsigned long long b1 = ~0ull, b2 = ~0ull;
-        for (int p0 = w.lo; p0 < w.hi; p0 += 64) {
-            const int p = p0 + lane;
-            unsigned long long key = ~0ull;
-            if (p < w.hi) {
-                const int idx = pj_candidate(w, Mp, keys, p, K, U);
-                if (idx >= 0 && !C[idx] && !taken[idx]) {
-                    const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)f * cap + idx) * 32);
-                    key = ((unsigned long long)ham256(q0, q1, d[0], d[1]) << 32) | ((unsigned long long)p << 16) |
-                          (unsigned)idx;
-                }
-            }
-            const unsigned long long c1 = wave_min_shfl(key);
-            const unsigned long long c2 = wave_min_shfl(key == c1 ? ~0ull : key);
-            if (c1 < b1) {   // merge: the multiset top two by (dist, position)
-                b2 = min(b1, c2);
-                b1 = c1;
-            } else {
-                b2 = min(b2, c1);
-            }
-        }
-        ReplayPick pk{-1, 0, 0};
-        if (b1 != ~0ull) {
-            pk.g = (int)(b1 & 0xFFFF);
-            const int bd2 = b2 == ~0ull ? 256 : (int)(b2 >> 32);
-            const int bl2 = b2 == ~0ull ? -1 : K[(int)(b2 & 0xFFFF)].octave;
-            pk.accept = pj_accept((int)(b1 >> 32), K[pk.g].octave, bd2, bl2, P.nnratio);
-        }
-        return pk;
-    };
-    const int count = replay_chunks<true, false>(n, np, res + (size_t)f * pcap, S, obs_of, accept_of, rescan);
-    if constexpr (!kBig)
-        for (int i = lane; i < n; i += 64) Mo[i] = S.mo[i];
-    if (lane == 0) nmatches[f] = count;
-}
+// ---- the searches ----
+// SearchByProjection(F, vpMapPoints, th): Frame::isInFrustum has projected the MapPoint already
+struct LocalMapSearch {
+    using Point = orbm_proj_point;
+    using Params = orbm_proj_params;
+    using ToInt = CastInt;
+    struct Ctx {};
+    static constexpr int kExtra = kStereoExtra;
+    static constexpr bool kClaims = true, kSecond = true;
 
-size_t proj_scratch_bytes(int nframes, int cap, int pcap)
-{
-    return (size_t)nframes * pj_grid_stride(cap) * 4 + (size_t)nframes * 4 + (size_t)nframes * pcap * sizeof(PjResult) + 256;
-}
-
-void launch_proj(const orbx_keypoint* kps, const uint8_t* desc, const float* uright, const uint8_t* claimed,
-                 const int* counts, int nframes, int cap, const orbm_proj_point* pts, const uint8_t* pdesc,
-                 const int* npts, int pcap, const orbm_proj_params& P, void* scratch, int* match, int* nmatches,
-                 hipStream_t s)
-{
-    uint32_t* gkeys = (uint32_t*)scratch;
-    int* gn = (int*)(gkeys + (size_t)nframes * pj_grid_stride(cap));
-    PjResult* res = (PjResult*)(((uintptr_t)(gn + nframes) + 15) & ~(uintptr_t)15);
-    launch_pj_grid(kps, counts, nframes, cap, P.min_x, P.min_y, P.grid_w_inv, P.grid_h_inv, gkeys, gn, s);
-    hipLaunchKernelGGL(k_pj_points, dim3((pcap + 256 / kSub - 1) / (256 / kSub), nframes), dim3(256), 0, s, kps, desc,
-                       uright, claimed, cap, pts, pdesc, npts, pcap, P, gkeys, gn, res);
-    auto resolve = [&](auto kern) {
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)replay_lds_bytes(cap));
-        hipLaunchKernelGGL(kern, dim3(nframes), dim3(64), replay_lds_bytes(cap), s, kps, desc, uright, claimed, counts,
-                           cap, pts, pdesc, npts, pcap, P, gkeys, gn, res, match, nmatches);
-    };
-    if (cap > kReplayLdsCap) resolve(k_pj_resolve<true>);
-    else resolve(k_pj_resolve<false>);
-}
-
-// =====================================================================================
-// Pose-projection searches: SearchByProjection(CurrentFrame, LastFrame) (:1396-1538),
-// SearchByProjection(CurrentFrame, pKF, sAlreadyFound) (:1540-1667), SearchByProjection(pKF,
-// Scw, ...) (:290-403), Fuse(pKF, ...) (:893-1043), Fuse(pKF, Scw, ...) (:1045-1168).
-//
-// J1 k_pj_grid     as above
-// J2 k_ps_points   one lane per MapPoint: project with the frame pose, scan the window in
-//                  GetFeaturesInArea order against the claims on entry (first minimum).
-//                  The Fuse overloads claim nothing during the search: they finish here.
-// J3 k_ps_resolve  one wave per frame replays the three searches in MapPoint order with
-//                  replay_chunks (above), then the rotation histogram from per-feature bin
-//                  masks in LDS.
-// Float arithmetic is oracle/orbref.c proj_* operation for operation (no contraction in this
-// file; the reference's GCC -march=native FMAs are explicit).
-// =====================================================================================
-
-// ps_x86_int, ps_row, PsCam / ps_camera and ps_predict_scale (MapPoint::PredictScale) are shared with
-// Frame::isInFrustum (orbx_frame.hip): orbx_device.hpp
-
-struct PsWin {
-    float u, v, r, ur;
-    int minLevel, maxLevel, cx0, cx1, cy0, cy1, lo, hi;
+    static __device__ __forceinline__ Ctx context(const float*, int, const Params&) { return Ctx{}; }
+    static __device__ __forceinline__ bool project(const Ctx&, const Point& M, const Params& P, ProjWindow& w)
+    {
+        const int level = M.level;
+        if (level < 0 || level >= 16) return false;   // outside mvScaleFactors: UB in the reference
+        float r = M.view_cos > 0.998 ? 2.5f : 4.0f;   // RadiusByViewingCos, src/ORBmatcher.cc:130-136
+        if (P.th != 1.0f) r *= P.th;
+        w.r = r * P.scale[level];
+        w.u = M.proj_x;
+        w.v = M.proj_y;
+        w.ur = M.proj_xr;
+        w.minLevel = level - 1;   // bCheckLevels is true for level >= 0
+        w.maxLevel = level;
+        return true;
+    }
+    static __device__ __forceinline__ bool rot(const Params&) { return false; }
+    static __device__ __forceinline__ int bin(const Point&, const orbx_keypoint&) { return 0; }
+    static __device__ __forceinline__ int oct(const orbx_keypoint& kp) { return kp.octave; }
+    // best (d1, level l1) against the second (d2, l2; 256, -1 = none)
+    static __device__ __forceinline__ bool accept(const Params& P, int d1, int l1, int d2, int l2)
+    {
+        if (!(d1 <= 100)) return false;   // TH_HIGH
+        if (l1 == l2 && (float)d1 > P.nnratio * (float)d2) return false;
+        return true;
+    }
+    static __device__ __forceinline__ int obs(const Point& M) { return (M.flags & 2) ? 1 : 0; }
 };
 
 // the per-MapPoint part before GetFeaturesInArea; false where the reference `continue`s
 template <int MODE>
 __device__ __forceinline__ bool ps_project(const PsCam& c, const orbm_map_point& M, const orbm_pose_params& P,
-                                           PsWin& w)
+                                           ProjWindow& w)
 {
     const float X = M.x, Y = M.y, Z = M.z;
     const float xc = ps_row(c.R, 1, X, Y, Z) + c.t[0];
@@ -655,253 +633,208 @@ __device__ __forceinline__ bool ps_project(const PsCam& c, const orbm_map_point&
     return true;
 }
 
-__device__ __forceinline__ bool ps_window(PsWin& w, const orbm_pose_params& P, const uint32_t* keys, int cap)
-{
-    const int cx0 = max(0, ps_x86_int(floorf((w.u - P.min_x - w.r) * P.grid_w_inv)));
-    if (cx0 >= kPjCols) return false;
-    const int cx1 = min(kPjCols - 1, ps_x86_int(ceilf((w.u - P.min_x + w.r) * P.grid_w_inv)));
-    if (cx1 < 0) return false;
-    w.cy0 = max(0, ps_x86_int(floorf((w.v - P.min_y - w.r) * P.grid_h_inv)));
-    if (w.cy0 >= kPjRows) return false;
-    w.cy1 = min(kPjRows - 1, ps_x86_int(ceilf((w.v - P.min_y + w.r) * P.grid_h_inv)));
-    if (w.cy1 < 0) return false;
-    w.cx0 = cx0;
-    w.cx1 = cx1;
-    w.lo = (int)keys[cap + cx0 * kPjRows];
-    w.hi = (int)keys[cap + (cx1 + 1) * kPjRows];
-    return true;
-}
-
-// feature index at key position p if it passes the mode's window / level / stereo tests
+// ps_x86_int, ps_row, PsCam / ps_camera and ps_predict_scale (MapPoint::PredictScale) are shared with
+// Frame::isInFrustum (orbx_frame.hip): orbx_device.hpp
 template <int MODE>
-__device__ __forceinline__ int ps_candidate(const PsWin& w, const uint32_t* keys, int p, const orbx_keypoint* K,
-                                            const float* U, const orbm_pose_params& P)
-{
-    const uint32_t key = keys[p];
-    const int iy = (int)(key >> 16) % kPjRows;
-    if (iy < w.cy0 || iy > w.cy1) return -1;
-    const int idx = (int)(key & 0xFFFF);
-    const orbx_keypoint kp = K[idx];
-    if (kp.octave < w.minLevel) return -1;
-    if (w.maxLevel >= 0 && kp.octave > w.maxLevel) return -1;
-    const float distx = kp.x - w.u, disty = kp.y - w.v;
-    if (!(fabsf(distx) < w.r && fabsf(disty) < w.r)) return -1;
-    if (MODE == ORBM_PROJ_LAST_FRAME) {   // :1475-1481
-        const float ur = U[idx];
-        if (ur > 0 && fabsf(w.ur - ur) > w.r) return -1;
+struct PoseSearch {
+    using Point = orbm_map_point;
+    using Params = orbm_pose_params;
+    using ToInt = X86Int;
+    using Ctx = PsCam;
+    static constexpr int kExtra = MODE == ORBM_PROJ_LAST_FRAME ? kStereoExtra : (MODE == ORBM_FUSE ? kChi2Extra : kNoExtra);
+    static constexpr bool kClaims = MODE <= ORBM_PROJ_SIM3, kSecond = false;
+
+    static __device__ __forceinline__ Ctx context(const float* pose, int f, const Params& P)
+    {
+        return ps_camera(MODE, pose + (size_t)f * 24, P);
     }
-    if (MODE == ORBM_FUSE) {   // :982-1006
-        const float ur = U[idx];
-        const float ex = w.u - kp.x, ey = w.v - kp.y;
-        const float is2 = P.inv_sigma2[kp.octave & 15];
-        if (ur >= 0) {
-            const float er = w.ur - ur;
-            const float e2 = __builtin_fmaf(er, er, __builtin_fmaf(ex, ex, ey * ey));
-            if ((double)(e2 * is2) > 7.8) return -1;
-        } else {
-            const float e2 = __builtin_fmaf(ex, ex, ey * ey);
-            if ((double)(e2 * is2) > 5.99) return -1;
-        }
+    static __device__ __forceinline__ bool project(const Ctx& c, const Point& M, const Params& P, ProjWindow& w)
+    {
+        return ps_project<MODE>(c, M, P, w);
     }
-    return idx;
-}
+    static __device__ __forceinline__ bool rot(const Params& P)
+    {
+        return (MODE == ORBM_PROJ_LAST_FRAME || MODE == ORBM_PROJ_KEYFRAME) && P.check_ori;
+    }
+    static __device__ __forceinline__ int bin(const Point& M, const orbx_keypoint& kp) { return rot_bin(M.angle, kp.angle); }
+    static __device__ __forceinline__ int oct(const orbx_keypoint&) { return 0; }
+    static __device__ __forceinline__ bool accept(const Params& P, int d1, int, int, int)
+    {
+        return d1 <= (MODE == ORBM_PROJ_LAST_FRAME ? 100 : (MODE == ORBM_PROJ_KEYFRAME ? P.orb_dist : 50));   // TH_HIGH / TH_LOW
+    }
+    // LAST_FRAME claims a feature only for a MapPoint with Observations() > 0 (:1471-1473); the
+    // other searches skip every feature already assigned (:1609-1610, :375-376)
+    static __device__ __forceinline__ int obs(const Point& M) { return MODE != ORBM_PROJ_LAST_FRAME || (M.flags & 2) ? 1 : 0; }
+};
 
-template <int MODE>
-__device__ __forceinline__ int ps_threshold(const orbm_pose_params& P)
+template <class S>
+__global__ __launch_bounds__(256) void k_points(const orbx_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc,
+                                                const float* __restrict__ uright, const uint8_t* __restrict__ claimed,
+                                                int cap, const float* __restrict__ pose,
+                                                const typename S::Point* __restrict__ pts,
+                                                const uint8_t* __restrict__ pdesc, const int* __restrict__ npts, int pcap,
+                                                typename S::Params P, const uint32_t* __restrict__ gkeys,
+                                                TopResult* __restrict__ res, int* __restrict__ match,
+                                                int* __restrict__ nmatches)
 {
-    return MODE == ORBM_PROJ_LAST_FRAME ? 100 : (MODE == ORBM_PROJ_KEYFRAME ? P.orb_dist : 50);   // TH_HIGH / TH_LOW
-}
-
-using PsResult = TopResult;   // bins filled for the rotation-checked searches
-
-template <int MODE>
-__global__ __launch_bounds__(256) void k_ps_points(const orbx_keypoint* __restrict__ kps,
-                                                   const uint8_t* __restrict__ desc, const float* __restrict__ uright,
-                                                   const uint8_t* __restrict__ claimed, int cap,
-                                                   const float* __restrict__ pose, const orbm_map_point* __restrict__ pts,
-                                                   const uint8_t* __restrict__ pdesc, const int* __restrict__ npts,
-                                                   int pcap, orbm_pose_params P, const uint32_t* __restrict__ gkeys,
-                                                   const int* __restrict__ gn, PsResult* __restrict__ res,
-                                                   int* __restrict__ match, int* __restrict__ nmatches)
-{
-    constexpr bool kSearch = MODE <= ORBM_PROJ_SIM3;
     const int f = blockIdx.y, m = blockIdx.x * (256 / kSub) + threadIdx.x / kSub, sub = threadIdx.x % kSub;
     if (m >= min(npts[f], pcap)) return;   // uniform over the kSub lanes of a MapPoint
     const size_t mo = (size_t)f * pcap + m;
-    int bestIdx = -1, accept = 0;
     TopK64 T64;
     T64.n = 0;
 #pragma unroll
     for (int k = 0; k < kTop; ++k) T64.e[k] = 0ull;
-    unsigned long long best = ~0ull;   // Fuse: first minimum as (dist, position, index)
-    const orbm_map_point M = pts[mo];
+    unsigned long long best = ~0ull;   // a search without claims: the first minimum
+    const typename S::Point M = pts[mo];
     bool scanned = false;
     if (M.flags & 1) {
-        const PsCam c = ps_camera(MODE, pose + (size_t)f * 24, P);
-        const uint32_t* keys = gkeys + (size_t)f * pj_grid_stride(cap);
-        PsWin w;
-        if (ps_project<MODE>(c, M, P, w) && ps_window(w, P, keys, cap)) {
+        const typename S::Ctx c = S::context(pose, f, P);
+        const FrameView F = frame_view(kps, desc, uright, claimed, gkeys, f, cap);
+        ProjWindow w;
+        if (S::project(c, M, P, w) && proj_window<typename S::ToInt>(w, P, F.keys, cap)) {
             scanned = true;
-            const orbx_keypoint* K = kps + (size_t)f * cap;
-            const float* U = uright + (size_t)f * cap;
-            const uint8_t* C = claimed + (size_t)f * cap;
             const uint4* qd = reinterpret_cast<const uint4*>(pdesc + mo * 32);
             const uint4 q0 = qd[0], q1 = qd[1];
-            const bool bins = kSearch && (MODE == ORBM_PROJ_LAST_FRAME || MODE == ORBM_PROJ_KEYFRAME) && P.check_ori;
-            for (int cx = w.cx0; cx <= w.cx1; ++cx) {   // GetFeaturesInArea order, rows cy0..cy1 only
-                const int a = (int)keys[cap + cx * kPjRows + w.cy0], b = (int)keys[cap + cx * kPjRows + w.cy1 + 1];
-                for (int p = a + sub; p < b; p += kSub) {
-                    const int idx = ps_candidate<MODE>(w, keys, p, K, U, P);
-                    if (idx < 0 || (kSearch && C[idx])) continue;
-                    const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)f * cap + idx) * 32);
-                    const int dist = ham256(q0, q1, d[0], d[1]);
-                    if (kSearch) {
-                        top64_insert(T64, top_key(top_entry(dist, bins ? rot_bin(M.angle, K[idx].angle) : 0, 0,
-                                                            idx),
-                                                  p));
-                    } else {
-                        const unsigned long long key =
-                            (unsigned long long)dist << 32 | (unsigned long long)p << 16 | (unsigned)idx;
-                        best = key < best ? key : best;
-                    }
-                }
-            }
+            const bool rot = S::rot(P);
+            if constexpr (S::kClaims)
+                walk_window<S>(w, F, sub, q0, q1, P, [&](int p, int idx, int dist) {
+                    top64_insert(T64, top_key(top_entry(dist, rot ? S::bin(M, F.K[idx]) : 0, S::oct(F.K[idx]), idx), p));
+                });
+            else
+                walk_window<S>(w, F, sub, q0, q1, P, [&](int p, int idx, int dist) {
+                    const unsigned long long key = first_key(dist, p, idx);
+                    best = key < best ? key : best;
+                });
         }
     }
-    TopK T;
-    if (kSearch) {
-        T = top_merge(T64);   // whole group: `scanned` is uniform over it
-        if (scanned && T.n > 0) {
-            bestIdx = top_idx(T.e[0]);
-            accept = top_dist(T.e[0]) <= ps_threshold<MODE>(P);
-        }
-    } else {
-        best = sub_min_u64(best);
-        if (best != ~0ull) {
-            bestIdx = (int)(best & 0xFFFF);
-            accept = (int)(best >> 32) <= ps_threshold<MODE>(P);
-        }
-    }
-    if (sub != 0) return;
-    if (kSearch) {
-        PsResult R;
+    if constexpr (S::kClaims) {
+        const TopK T = top_merge(T64);   // whole group: `scanned` is uniform over it
+        if (sub != 0) return;
+        TopResult R;
 #pragma unroll
         for (int k = 0; k < kTop; ++k) R.e[k] = T.e[k];
         R.n = T.n;
-        R.accept = accept;
+        // the scan's best / second are the first two entries (multiset top two, first wins ties)
+        R.accept = scanned && T.n > 0 &&
+                   S::accept(P, top_dist(T.e[0]), top_oct(T.e[0]), T.n > 1 ? top_dist(T.e[1]) : 256,
+                             T.n > 1 ? top_oct(T.e[1]) : -1);
         res[mo] = R;
     } else {
-        match[mo] = accept ? bestIdx : -1;
+        best = sub_min_u64(best);
+        if (sub != 0) return;
+        const bool accept = best != ~0ull && S::accept(P, (int)(best >> 32), 0, 256, -1);
+        match[mo] = accept ? (int)(best & 0xFFFF) : -1;
         if (accept) atomicAdd(&nmatches[f], 1);
     }
 }
 
-template <int MODE, bool kBig>
-__global__ __launch_bounds__(64) void k_ps_resolve(const orbx_keypoint* __restrict__ kps,
-                                                   const uint8_t* __restrict__ desc, const float* __restrict__ uright,
-                                                   const uint8_t* __restrict__ claimed, const int* __restrict__ counts,
-                                                   int cap, const float* __restrict__ pose,
-                                                   const orbm_map_point* __restrict__ pts,
-                                                   const uint8_t* __restrict__ pdesc, const int* __restrict__ npts,
-                                                   int pcap, orbm_pose_params P, const uint32_t* __restrict__ gkeys,
-                                                   const int* __restrict__ gn, const PsResult* __restrict__ res,
-                                                   int* __restrict__ match, int* __restrict__ nmatches)
+template <class S, bool kBig>
+__global__ __launch_bounds__(64) void k_resolve(const orbx_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc,
+                                                const float* __restrict__ uright, const uint8_t* __restrict__ claimed,
+                                                const int* __restrict__ counts, int cap, const float* __restrict__ pose,
+                                                const typename S::Point* __restrict__ pts,
+                                                const uint8_t* __restrict__ pdesc, const int* __restrict__ npts, int pcap,
+                                                typename S::Params P, const uint32_t* __restrict__ gkeys,
+                                                const TopResult* __restrict__ res, int* __restrict__ match,
+                                                int* __restrict__ nmatches)
 {
-    constexpr bool kRotMode = MODE == ORBM_PROJ_LAST_FRAME || MODE == ORBM_PROJ_KEYFRAME;
     const int f = blockIdx.x, lane = threadIdx.x;
     const int n = min(counts[f], cap), np = min(npts[f], pcap);
     int* Mo = match + (size_t)f * cap;
-    const ReplayLds S = replay_lds<kBig>(cap, Mo);
-    const uint32_t* keys = gkeys + (size_t)f * pj_grid_stride(cap);
-    const orbx_keypoint* K = kps + (size_t)f * cap;
-    const float* U = uright + (size_t)f * cap;
-    const uint8_t* C = claimed + (size_t)f * cap;
-    const orbm_map_point* Pf = pts + (size_t)f * pcap;
-    const PsCam cam = ps_camera(MODE, pose + (size_t)f * 24, P);
-    const bool rot = kRotMode && P.check_ori;
-    const int thr = ps_threshold<MODE>(P);
-    // LAST_FRAME claims a feature only for a MapPoint with Observations() > 0 (:1471-1473); the
-    // other searches skip every feature already assigned (:1609-1610, :375-376)
-    auto obs_of = [&](int m) { return MODE != ORBM_PROJ_LAST_FRAME || (Pf[m].flags & 2) ? 1 : 0; };
-    auto accept_of = [&](uint32_t c1, bool, uint32_t) { return top_dist(c1) <= thr; };
+    const ReplayLds L = replay_lds<kBig>(cap, Mo);
+    const FrameView F = frame_view(kps, desc, uright, claimed, gkeys, f, cap);
+    const typename S::Point* Pf = pts + (size_t)f * pcap;
+    const typename S::Ctx c = S::context(pose, f, P);
+    const bool rot = S::rot(P);
+    auto obs_of = [&](int m) { return S::obs(Pf[m]); };
+    auto accept_of = [&](uint32_t c1, bool has2, uint32_t c2) {
+        return S::accept(P, top_dist(c1), top_oct(c1), has2 ? top_dist(c2) : 256, has2 ? top_oct(c2) : -1);
+    };
     auto rescan = [&](int m, const uint8_t* taken) {
-        const orbm_map_point Mp = Pf[m];
-        PsWin w;
-        ps_project<MODE>(cam, Mp, P, w);   // true and non-empty: J2 found candidates in it
-        ps_window(w, P, keys, cap);
+        const typename S::Point Mp = Pf[m];
+        ProjWindow w;
+        S::project(c, Mp, P, w);   // true and non-empty: J2 found candidates in it
+        proj_window<typename S::ToInt>(w, P, F.keys, cap);
         const uint4* qd = reinterpret_cast<const uint4*>(pdesc + ((size_t)f * pcap + m) * 32);
         const uint4 q0 = qd[0], q1 = qd[1];
-        unsigned long long b1 = ~0ull;
-        for (int p0 = w.lo; p0 < w.hi; p0 += 64) {
-            const int p = p0 + lane;
-            unsigned long long key = ~0ull;
-            if (p < w.hi) {
-                const int idx = ps_candidate<MODE>(w, keys, p, K, U, P);
-                if (idx >= 0 && !C[idx] && !taken[idx]) {
-                    const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)f * cap + idx) * 32);
-                    key = ((unsigned long long)ham256(q0, q1, d[0], d[1]) << 32) | ((unsigned long long)p << 16) |
-                          (unsigned)idx;
-                }
-            }
-            const unsigned long long c1 = wave_min_shfl(key);
-            b1 = c1 < b1 ? c1 : b1;
-        }
+        unsigned long long b1, b2;
+        rescan_window<S>(w, F, taken, q0, q1, P, b1, b2);
         ReplayPick pk{-1, 0, 0};
         if (b1 != ~0ull) {
             pk.g = (int)(b1 & 0xFFFF);
-            pk.accept = (int)(b1 >> 32) <= thr;
-            if (rot) pk.bin = rot_bin(Mp.angle, K[pk.g].angle);
+            const bool has2 = b2 != ~0ull;
+            pk.accept = S::accept(P, (int)(b1 >> 32), S::oct(F.K[pk.g]), has2 ? (int)(b2 >> 32) : 256,
+                                  has2 ? S::oct(F.K[(int)(b2 & 0xFFFF)]) : -1);
+            if (rot) pk.bin = S::bin(Mp, F.K[pk.g]);
         }
         return pk;
     };
-    int count = rot ? replay_chunks<false, true>(n, np, res + (size_t)f * pcap, S, obs_of, accept_of, rescan)
-                    : replay_chunks<false, false>(n, np, res + (size_t)f * pcap, S, obs_of, accept_of, rescan);
+    int count = rot ? replay_chunks<S::kSecond, true>(n, np, res + (size_t)f * pcap, L, obs_of, accept_of, rescan)
+                    : replay_chunks<S::kSecond, false>(n, np, res + (size_t)f * pcap, L, obs_of, accept_of, rescan);
     uint32_t drop = 0u;   // the bins outside the three maxima
     if (rot) {            // ComputeThreeMaxima (:1679-1723); every match in another bin is undone
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < kHisto; ++i) {
-            const int h = S.hist[i];
-            if (h > max1) { max3 = max2; max2 = max1; max1 = h; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (h > max2) { max3 = max2; max2 = h; ind3 = ind2; ind2 = i; }
-            else if (h > max3) { max3 = h; ind3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
+        int ind1, ind2, ind3;
+        three_maxima(L.hist, ind1, ind2, ind3);
         drop = 0x3FFFFFFFu;
         if (ind1 >= 0) drop &= ~(1u << ind1);
         if (ind2 >= 0) drop &= ~(1u << ind2);
         if (ind3 >= 0) drop &= ~(1u << ind3);
-        for (int i = 0; i < 30; ++i)
-            if ((drop >> i) & 1u) count -= S.hist[i];
+        for (int i = 0; i < kHisto; ++i)
+            if ((drop >> i) & 1u) count -= L.hist[i];
     }
-    for (int i = lane; i < n; i += 64) Mo[i] = (S.bins[i] & drop) ? -2 : S.mo[i];   // NULL-ed by the filter (in place when kBig)
+    if (rot || !kBig)   // kBig: the assignments are in the output row already; the filter NULLs in place
+        for (int i = lane; i < n; i += 64) Mo[i] = (L.bins[i] & drop) ? -2 : L.mo[i];
     if (lane == 0) nmatches[f] = count;
 }
 
-size_t pose_scratch_bytes(int nframes, int cap, int pcap)
+size_t proj_scratch_bytes(int nframes, int cap, int pcap)
 {
-    return (size_t)nframes * pj_grid_stride(cap) * 4 + (size_t)nframes * 4 + (size_t)nframes * pcap * sizeof(PsResult) + 256;
+    return GridScratch(nullptr, nframes, cap, (size_t)nframes * pcap * sizeof(TopResult)).bytes;
 }
 
-template <int MODE>
-static void ps_launch(const orbx_keypoint* kps, const uint8_t* desc, const float* uright, const uint8_t* claimed,
-                      const int* counts, int nframes, int cap, const float* pose, const orbm_map_point* pts,
-                      const uint8_t* pdesc, const int* npts, int pcap, const orbm_pose_params& P,
-                      const uint32_t* gkeys, const int* gn, PsResult* res, int* match, int* nmatches,
-                      hipStream_t s)
+// J1, J2 and, for a search with claims, J3 of one call
+template <class S>
+static void launch_search(const orbx_keypoint* kps, const uint8_t* desc, const float* uright, const uint8_t* claimed,
+                          const int* counts, int nframes, int cap, const float* pose, const typename S::Point* pts,
+                          const uint8_t* pdesc, const int* npts, int pcap, const typename S::Params& P, void* scratch,
+                          int* match, int* nmatches, hipStream_t s)
 {
-    if (MODE >= ORBM_FUSE) hipMemsetAsync(nmatches, 0, sizeof(int) * (size_t)nframes, s);
-    hipLaunchKernelGGL(k_ps_points<MODE>, dim3((pcap + 256 / kSub - 1) / (256 / kSub), nframes), dim3(256), 0, s,
-                       kps, desc, uright,
-                       claimed, cap, pose, pts, pdesc, npts, pcap, P, gkeys, gn, res, match, nmatches);
-    if (MODE <= ORBM_PROJ_SIM3) {
+    const GridScratch sc(scratch, nframes, cap, 0);
+    TopResult* res = (TopResult*)sc.tail;
+    launch_pj_grid(kps, counts, nframes, cap, P, sc.gkeys, s);
+    if (!S::kClaims) hipMemsetAsync(nmatches, 0, sizeof(int) * (size_t)nframes, s);
+    hipLaunchKernelGGL(k_points<S>, dim3((pcap + 256 / kSub - 1) / (256 / kSub), nframes), dim3(256), 0, s, kps, desc,
+                       uright, claimed, cap, pose, pts, pdesc, npts, pcap, P, sc.gkeys, res, match, nmatches);
+    if constexpr (S::kClaims) {
         auto resolve = [&](auto kern) {
             hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)replay_lds_bytes(cap));
             hipLaunchKernelGGL(kern, dim3(nframes), dim3(64), replay_lds_bytes(cap), s, kps, desc, uright, claimed,
-                               counts, cap, pose, pts, pdesc, npts, pcap, P, gkeys, gn, res, match, nmatches);
+                               counts, cap, pose, pts, pdesc, npts, pcap, P, sc.gkeys, res, match, nmatches);
         };
-        if (cap > kReplayLdsCap) resolve(k_ps_resolve<MODE, true>);
-        else resolve(k_ps_resolve<MODE, false>);
+        if (cap > kReplayLdsCap) resolve(k_resolve<S, true>);
+        else resolve(k_resolve<S, false>);
+    }
+}
+
+void launch_proj(const orbx_keypoint* kps, const uint8_t* desc, const float* uright, const uint8_t* claimed,
+                 const int* counts, int nframes, int cap, const orbm_proj_point* pts, const uint8_t* pdesc,
+                 const int* npts, int pcap, const orbm_proj_params& P, void* scratch, int* match, int* nmatches,
+                 hipStream_t s)
+{
+    launch_search<LocalMapSearch>(kps, desc, uright, claimed, counts, nframes, cap, nullptr, pts, pdesc, npts, pcap, P,
+                                  scratch, match, nmatches, s);
+}
+
+// fn(PoseSearch<mode>{})
+template <class Fn>
+static void with_pose_search(int mode, Fn fn)
+{
+    switch (mode) {
+    case ORBM_PROJ_LAST_FRAME: return fn(PoseSearch<ORBM_PROJ_LAST_FRAME>{});
+    case ORBM_PROJ_KEYFRAME: return fn(PoseSearch<ORBM_PROJ_KEYFRAME>{});
+    case ORBM_PROJ_SIM3: return fn(PoseSearch<ORBM_PROJ_SIM3>{});
+    case ORBM_FUSE: return fn(PoseSearch<ORBM_FUSE>{});
+    default: return fn(PoseSearch<ORBM_FUSE_SIM3>{});
     }
 }
 
@@ -910,32 +843,10 @@ void launch_pose_search(int mode, const orbx_keypoint* kps, const uint8_t* desc,
                         const orbm_map_point* pts, const uint8_t* pdesc, const int* npts, int pcap,
                         const orbm_pose_params& P, void* scratch, int* match, int* nmatches, hipStream_t s)
 {
-    uint32_t* gkeys = (uint32_t*)scratch;
-    int* gn = (int*)(gkeys + (size_t)nframes * pj_grid_stride(cap));
-    PsResult* res = (PsResult*)(((uintptr_t)(gn + nframes) + 15) & ~(uintptr_t)15);
-    launch_pj_grid(kps, counts, nframes, cap, P.min_x, P.min_y, P.grid_w_inv, P.grid_h_inv, gkeys, gn, s);
-    switch (mode) {
-    case ORBM_PROJ_LAST_FRAME:
-        ps_launch<ORBM_PROJ_LAST_FRAME>(kps, desc, uright, claimed, counts, nframes, cap, pose, pts, pdesc, npts, pcap,
-                                        P, gkeys, gn, res, match, nmatches, s);
-        break;
-    case ORBM_PROJ_KEYFRAME:
-        ps_launch<ORBM_PROJ_KEYFRAME>(kps, desc, uright, claimed, counts, nframes, cap, pose, pts, pdesc, npts, pcap,
-                                      P, gkeys, gn, res, match, nmatches, s);
-        break;
-    case ORBM_PROJ_SIM3:
-        ps_launch<ORBM_PROJ_SIM3>(kps, desc, uright, claimed, counts, nframes, cap, pose, pts, pdesc, npts, pcap, P,
-                                  gkeys, gn, res, match, nmatches, s);
-        break;
-    case ORBM_FUSE:
-        ps_launch<ORBM_FUSE>(kps, desc, uright, claimed, counts, nframes, cap, pose, pts, pdesc, npts, pcap, P, gkeys,
-                             gn, res, match, nmatches, s);
-        break;
-    default:
-        ps_launch<ORBM_FUSE_SIM3>(kps, desc, uright, claimed, counts, nframes, cap, pose, pts, pdesc, npts, pcap, P,
-                                  gkeys, gn, res, match, nmatches, s);
-        break;
-    }
+    with_pose_search(mode, [&](auto search) {
+        launch_search<decltype(search)>(kps, desc, uright, claimed, counts, nframes, cap, pose, pts, pdesc, npts, pcap,
+                                        P, scratch, match, nmatches, s);
+    });
 }
 
 // =====================================================================================
@@ -981,7 +892,7 @@ __device__ __forceinline__ S3Rel s3_relative(int dir, const float* __restrict__ 
 // :1226-1257 / :1306-1337; false where the reference `continue`s.  Unlike ps_project the distance
 // test is on cv::norm of the camera-frame point, and there is no viewing-angle test.
 __device__ __forceinline__ bool s3_project(const float* __restrict__ Tsw, const S3Rel& c, const orbm_map_point& M,
-                                           const orbm_pose_params& P, PsWin& w)
+                                           const orbm_pose_params& P, ProjWindow& w)
 {
     const float a0 = ps_row(Tsw, 1, M.x, M.y, M.z) + Tsw[3];
     const float a1 = ps_row(Tsw + 4, 1, M.x, M.y, M.z) + Tsw[7];
@@ -1012,6 +923,14 @@ __device__ __forceinline__ bool s3_project(const float* __restrict__ Tsw, const 
     return true;
 }
 
+// the window search of one direction, as the Fuse overloads: no claims, no extra test, the first minimum
+struct Sim3Search {
+    using Params = orbm_pose_params;
+    using ToInt = X86Int;
+    static constexpr int kExtra = kNoExtra;
+    static constexpr bool kClaims = false;
+};
+
 __global__ __launch_bounds__(256) void k_s3_points(const orbx_keypoint* __restrict__ kps,
                                                    const uint8_t* __restrict__ desc,
                                                    const orbm_map_point* __restrict__ mps,
@@ -1037,23 +956,16 @@ __global__ __launch_bounds__(256) void k_s3_points(const orbx_keypoint* __restri
         const orbm_map_point M = mps[so];
         if (M.flags & 1) {
             const S3Rel c = s3_relative(dir, sim3 + (size_t)p * 13);
-            const uint32_t* keys = gkeys + (size_t)ft * pj_grid_stride(cap);
-            PsWin w;
-            if (s3_project(pose + (size_t)fs * 12, c, M, P, w) && ps_window(w, P, keys, cap)) {
-                const orbx_keypoint* K = kps + (size_t)ft * cap;
+            const size_t to = (size_t)ft * cap;
+            const FrameView F{gkeys + (size_t)ft * pj_grid_stride(cap), kps + to, nullptr, nullptr, desc + to * 32, cap};
+            ProjWindow w;
+            if (s3_project(pose + (size_t)fs * 12, c, M, P, w) && proj_window<Sim3Search::ToInt>(w, P, F.keys, cap)) {
                 const uint4* qd = reinterpret_cast<const uint4*>(mpdesc + so * 32);
                 const uint4 q0 = qd[0], q1 = qd[1];
-                for (int cx = w.cx0; cx <= w.cx1; ++cx) {   // GetFeaturesInArea order, rows cy0..cy1 only
-                    const int a = (int)keys[cap + cx * kPjRows + w.cy0], b = (int)keys[cap + cx * kPjRows + w.cy1 + 1];
-                    for (int q = a + sub; q < b; q += kSub) {
-                        const int idx = ps_candidate<ORBM_FUSE_SIM3>(w, keys, q, K, nullptr, P);
-                        if (idx < 0) continue;
-                        const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)ft * cap + idx) * 32);
-                        const unsigned long long key = (unsigned long long)ham256(q0, q1, d[0], d[1]) << 32 |
-                                                       (unsigned long long)q << 16 | (unsigned)idx;
-                        best = key < best ? key : best;
-                    }
-                }
+                walk_window<Sim3Search>(w, F, sub, q0, q1, P, [&](int q, int idx, int dist) {
+                    const unsigned long long key = first_key(dist, q, idx);
+                    best = key < best ? key : best;
+                });
             }
         }
     }
@@ -1080,7 +992,7 @@ __global__ __launch_bounds__(256) void k_s3_agree(const int* __restrict__ match1
 
 size_t sim3_scratch_bytes(int nkf, int npairs, int cap)
 {
-    return (size_t)nkf * pj_grid_stride(cap) * 4 + (size_t)nkf * 4 + (size_t)2 * npairs * cap * 4 + 256;
+    return GridScratch(nullptr, nkf, cap, (size_t)2 * npairs * cap * 4).bytes;
 }
 
 void launch_search_by_sim3(const orbx_keypoint* kps, const uint8_t* desc, const orbm_map_point* mps,
@@ -1089,16 +1001,15 @@ void launch_search_by_sim3(const orbx_keypoint* kps, const uint8_t* desc, const 
                            const uint8_t* already2, int npairs, const orbm_pose_params& P, void* scratch, int* match12,
                            int* nfound, int* match1, int* match2, hipStream_t s)
 {
-    uint32_t* gkeys = (uint32_t*)scratch;
-    int* gn = (int*)(gkeys + (size_t)nkf * pj_grid_stride(cap));
-    int* tmp = gn + nkf;
+    const GridScratch sc(scratch, nkf, cap, 0);
+    int* tmp = (int*)sc.tail;
     if (!match1) match1 = tmp;
     if (!match2) match2 = tmp + (size_t)npairs * cap;
-    launch_pj_grid(kps, counts, nkf, cap, P.min_x, P.min_y, P.grid_w_inv, P.grid_h_inv, gkeys, gn, s);
+    launch_pj_grid(kps, counts, nkf, cap, P, sc.gkeys, s);
     hipMemsetAsync(nfound, 0, sizeof(int) * (size_t)npairs, s);
     hipLaunchKernelGGL(k_s3_points, dim3((cap + 256 / kSub - 1) / (256 / kSub), npairs, 2), dim3(256), 0, s, kps, desc,
-                       mps, mpdesc, counts, nkf, cap, pose, pair_a, pair_b, sim3, already1, already2, P, gkeys, match1,
-                       match2);
+                       mps, mpdesc, counts, nkf, cap, pose, pair_a, pair_b, sim3, already1, already2, P, sc.gkeys,
+                       match1, match2);
     hipLaunchKernelGGL(k_s3_agree, dim3((cap + 255) / 256, npairs), dim3(256), 0, s, match1, match2, cap, match12,
                        nfound);
 }

@@ -612,20 +612,13 @@ def test_gpu_project_search_host(orbref, cuda, mode, ci, seed):
     assert n == wn and np.array_equal(m, wm)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("mode", MODES)
-def test_gpu_project_search_batch(orbref, cuda, mode):
-    """Four frames with their own poses in one device call."""
+def _device_batch(cuda, mode, scenes, pp, cap, pcap):
+    """One orbm_project_search_device call over the scenes as frames of stride cap / pcap:
+    (nmatches[B], match[B, cap or pcap]) as numpy."""
     import ctypes
     import torch
     import orbx
-    ci = 1 if mode in ("last_frame", "keyframe") else 0
-    cases = [case(mode, ci, s) for s in range(4)]
-    scenes = [c[0] for c in cases]
-    pp = cases[0][1]
     B = len(scenes)
-    cap = max(len(s[0]) for s in scenes)
-    pcap = max(len(s[6]) for s in scenes)
     kps = np.zeros((B, cap), orbx.KEYPOINT_DTYPE)
     desc = np.zeros((B, cap, 32), np.uint8)
     ur = np.zeros((B, cap), np.float32)
@@ -652,10 +645,22 @@ def test_gpu_project_search_batch(orbref, cuda, mode):
                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0
     torch.cuda.synchronize()
+    return nm.cpu().numpy(), match.cpu().numpy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+def test_gpu_project_search_batch(orbref, cuda, mode):
+    """Four frames with their own poses in one device call."""
+    ci = 1 if mode in ("last_frame", "keyframe") else 0
+    cases = [case(mode, ci, s) for s in range(4)]
+    scenes = [c[0] for c in cases]
+    pp = cases[0][1]
+    nm, match = _device_batch(cuda, mode, scenes, pp, max(len(s[0]) for s in scenes), max(len(s[6]) for s in scenes))
     for b, sc in enumerate(scenes):
         wn, wm = run_oracle(mode, sc, pp)
         assert int(nm[b]) == wn
-        assert np.array_equal(match[b, :len(wm)].cpu().numpy(), wm)
+        assert np.array_equal(match[b, :len(wm)], wm)
 
 
 def _chain(orbref):
@@ -690,3 +695,113 @@ def test_gpu_claim_chain(orbref, cuda, mode):
                                                         orbx.PoseParams.from_buffer_copy(pp))
     wn, wm = orbref.project_search(mode, kps, desc, ur, cl, pose, pts, pd, pp)
     assert n == wn == 12 and np.array_equal(m, wm)
+
+
+# ---- a frame stride above the 8192 features whose assignments fit LDS: the replay writes the output row,
+# and the rotation filter of the two searches below NULLs matches in that row in place
+BIG_CAP, BIG_PCAP = 8256, 900
+BIG_MODES = ["last_frame", "keyframe"]
+
+
+def _big_stride_frames(orbref, mode):
+    """The claim chain, then seeded case 0 of the mode, under that case's parameters (check_ori = 1)."""
+    sc, pp = case(mode, 0, 0)
+    kps, desc, ur, cl, pose, pts, pd = _chain(orbref)
+    assert pp.check_ori == 1
+    return [(kps, desc, ur, cl, pose, pose[:12].reshape(3, 4), pts, pd), sc], pp
+
+
+def _exhausted(match, desc, pd, m):
+    """The eight nearest features of MapPoint m's descriptor (its candidate list) belong to MapPoints before it."""
+    d = [int(np.unpackbits(pd ^ desc[i]).sum()) for i in range(len(desc))]
+    first8 = sorted(range(len(desc)), key=lambda i: (d[i], i))[:8]
+    return all(0 <= match[i] < m for i in first8)
+
+
+@pytest.mark.parametrize("mode", BIG_MODES)
+def test_big_stride_reference_not_trivial(orbref, mode):
+    """The inputs of test_gpu_big_stride: every frame has matches, the seeded frame loses some to the
+    rotation filter, and in the chain frame (all twelve features in every window, distinct distances)
+    a MapPoint finds its first eight candidates claimed."""
+    frames, pp = _big_stride_frames(orbref, mode)
+    assert max(len(f[0]) for f in frames) <= BIG_CAP and max(len(f[6]) for f in frames) <= BIG_PCAP
+    n0, m0 = run_oracle(mode, frames[0], pp)
+    n1, m1 = run_oracle(mode, frames[1], pp)
+    assert n0 == 12 and list(m0) == list(range(12))
+    assert sum(_exhausted(m0, frames[0][1], frames[0][7][i], i) for i in range(14)) >= 4   # MapPoints 8..13
+    assert n1 > 30 and (m1 >= 0).sum() >= 1 and (m1 == -2).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", BIG_MODES)
+def test_gpu_big_stride(orbref, cuda, mode):
+    frames, pp = _big_stride_frames(orbref, mode)
+    nm, match = _device_batch(cuda, mode, frames, pp, BIG_CAP, BIG_PCAP)
+    for b, sc in enumerate(frames):
+        wn, wm = run_oracle(mode, sc, pp)
+        assert int(nm[b]) == wn
+        assert np.array_equal(match[b, :len(wm)], wm)
+
+
+# ---- ComputeThreeMaxima at its edges, through the keyframe search
+def _rot_scene(orbref, hist):
+    """hist[b] isolated features matched by one MapPoint each, at an angle difference of 30 b degrees:
+    rotHist[b] gets hist[b] matches (b <= 11).  An empty hist: one MapPoint whose descriptor is too far."""
+    bins = [b for b, c in enumerate(hist) for _ in range(c)]
+    xy = [(40.0 + 24 * (i % 20), 40.0 + 24 * (i // 20)) for i in range(max(len(bins), 1))]
+    kps = _tiny(orbref, xy)
+    pts = np.concatenate([_point_at(orbref, x, y, 10) for x, y in xy])
+    pts["angle"][:len(bins)] = [30.0 * b for b in bins]
+    pd = np.zeros((len(xy), 32), np.uint8)
+    if not bins:
+        pd[:] = 0xFF
+    pose = np.concatenate([np.hstack([np.eye(3), np.zeros((3, 1))]).ravel()] * 2).astype(np.float32)
+    sc = (kps, np.zeros((len(xy), 32), np.uint8), np.full(len(xy), -1, np.float32), np.zeros(len(xy), np.uint8), pose,
+          pose[:12].reshape(3, 4), pts, pd)
+    return sc, bins
+
+
+def _hist(**bins):
+    h = [0] * 30
+    for b, c in bins.items():
+        h[int(b[1:])] = c
+    return h
+
+
+THREE_MAXIMA_EDGES = [   # (rotHist sizes, ComputeThreeMaxima's ind1, ind2, ind3)
+    (_hist(), (-1, -1, -1)),                              # all bins empty
+    (_hist(b2=3, b5=3, b7=1, b9=1), (2, 5, 7)),           # equal maxima: the first bin wins each place
+    (_hist(b1=20, b4=2, b6=1), (1, 4, -1)),               # max2 == 0.1f * max1 stays, max3 below it goes
+    (_hist(b1=21, b4=2, b6=1), (1, -1, -1)),              # max2 below 0.1f * max1 takes ind3 with it
+]
+
+
+def _check_three_maxima(hist, want, sc, bins, n, m):
+    assert three_maxima(hist) == want
+    keep = [b in want for b in bins]
+    assert n == sum(keep)
+    assert list(m[:len(bins)]) == [i if k else -2 for i, k in enumerate(keep)]   # feature i <- MapPoint i
+    if not bins:
+        assert list(m) == [-1]
+
+
+@pytest.mark.parametrize("hist,want", THREE_MAXIMA_EDGES)
+def test_three_maxima_edges(orbref, hist, want):
+    sc, bins = _rot_scene(orbref, hist)
+    pp = params(th=3.0, orb_dist=100)
+    n, m = run_oracle("keyframe", sc, pp)
+    pn, pm = run_py("keyframe", sc, pp)
+    assert n == pn and list(m) == pm
+    _check_three_maxima(hist, want, sc, bins, n, m)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hist,want", THREE_MAXIMA_EDGES)
+def test_gpu_three_maxima_edges(orbref, cuda, hist, want):
+    import orbx
+    sc, bins = _rot_scene(orbref, hist)
+    kps, desc, ur, cl, pose, Scw, pts, pd = sc
+    pp = params(th=3.0, orb_dist=100)
+    n, m = orbx.ORBmatcher(0.9, True).project_search(MODE_ID["keyframe"], kps, desc, ur, cl, pose, pts, pd,
+                                                      orbx.PoseParams.from_buffer_copy(pp))
+    _check_three_maxima(hist, want, sc, bins, n, m)

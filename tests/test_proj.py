@@ -147,15 +147,13 @@ def test_gpu_search_by_projection_host(orbref, cuda, seed, th):
     assert n == wn and np.array_equal(m, wm)
 
 
-@pytest.mark.gpu
-def test_gpu_search_by_projection_batch(orbref, cuda):
+def _device_batch(cuda, scenes, cap, pcap, th, nnratio):
+    """One orbm_search_by_projection_device call over the scenes as frames of stride cap / pcap:
+    (nmatches[B], match[B, cap]) as numpy."""
     import ctypes
     import torch
     import orbx
-    scenes = [scene(s, n_kp=500 + 50 * s, n_mp=700 + 40 * s) for s in range(4)]
     B = len(scenes)
-    cap = max(len(s[0]) for s in scenes)
-    pcap = max(len(s[5]) for s in scenes)
     kps = np.zeros((B, cap), orbx.KEYPOINT_DTYPE)
     desc = np.zeros((B, cap, 32), np.uint8)
     ur = np.zeros((B, cap), np.float32)
@@ -176,17 +174,26 @@ def test_gpu_search_by_projection_batch(orbref, cuda):
     dp, dpd, dn, dnp = T(pts.view(np.int32).reshape(B, pcap, 6)), T(pdesc), T(counts), T(npts)
     match = torch.empty((B, cap), dtype=torch.int32, device=cuda)
     nm = torch.empty((B,), dtype=torch.int32, device=cuda)
-    prm = orbx.proj_params(scenes[0][4], SCALE, 3.0, 0.8)
+    prm = orbx.proj_params(scenes[0][4], SCALE, th, nnratio)
     P = lambda t: ctypes.c_void_p(t.data_ptr())
     rc = orbx.lib.orbm_search_by_projection_device(P(dk), P(dd), P(du), P(dc), P(dn), B, cap, P(dp), P(dpd), P(dnp),
                                                     pcap, ctypes.byref(prm), P(match), P(nm),
                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0
     torch.cuda.synchronize()
+    return nm.cpu().numpy(), match.cpu().numpy()
+
+
+@pytest.mark.gpu
+def test_gpu_search_by_projection_batch(orbref, cuda):
+    scenes = [scene(s, n_kp=500 + 50 * s, n_mp=700 + 40 * s) for s in range(4)]
+    cap = max(len(s[0]) for s in scenes)
+    pcap = max(len(s[5]) for s in scenes)
+    nm, match = _device_batch(cuda, scenes, cap, pcap, 3.0, 0.8)
     for b, (k, d, u, c, g, p, pd) in enumerate(scenes):
         wn, wm = orbref.search_by_projection(k, d, u, c, g, SCALE, p, pd, 3.0, 0.8)
         assert int(nm[b]) == wn
-        assert np.array_equal(match[b, :len(k)].cpu().numpy(), wm)
+        assert np.array_equal(match[b, :len(k)], wm)
 
 
 def _chain_scene(orbref):
@@ -220,3 +227,43 @@ def test_gpu_claim_chain(orbref, cuda):
     kps, desc, ur, cl, grid, pts, pdesc = _chain_scene(orbref)
     n, m = orbx.ORBmatcher(0.99).SearchByProjection(kps, desc, ur, cl, grid, SCALE, pts, pdesc, 3.0)
     assert n == 12 and list(m) == list(range(12))
+
+
+BIG_CAP = 8256   # a frame stride above the 8192 features whose assignments fit LDS: the replay writes the output row
+
+
+def _big_stride_frames(orbref):
+    return [_chain_scene(orbref), scene(1)], 900, 3.0, 0.99
+
+
+def _exhausted(match, desc, pd, m):
+    """The eight nearest features of MapPoint m's descriptor (its candidate list) belong to MapPoints before it."""
+    d = [int(np.unpackbits(pd ^ desc[i]).sum()) for i in range(len(desc))]
+    first8 = sorted(range(len(desc)), key=lambda i: (d[i], i))[:8]
+    return all(0 <= match[i] < m for i in first8)
+
+
+def test_big_stride_reference_not_trivial(orbref):
+    """The inputs of test_gpu_big_stride: every frame has matches, and in the chain frame (all twelve
+    features in every window, distinct distances) a MapPoint finds its first eight candidates claimed."""
+    frames, pcap, th, nnratio = _big_stride_frames(orbref)
+    assert max(len(f[0]) for f in frames) <= BIG_CAP and max(len(f[5]) for f in frames) <= pcap
+    for k, d, u, c, g, p, pd in frames:
+        n, m = orbref.search_by_projection(k, d, u, c, g, SCALE, p, pd, th, nnratio)
+        assert n >= 1 and (m >= 0).sum() >= 1
+    k, d, u, c, g, p, pd = frames[0]
+    n, m = orbref.search_by_projection(k, d, u, c, g, SCALE, p, pd, th, nnratio)
+    assert n == 12 and list(m) == list(range(12))
+    assert sum(_exhausted(m, d, pd[i], i) for i in range(len(p))) >= 4          # MapPoints 8..11 (and 12, 13)
+
+
+@pytest.mark.gpu
+def test_gpu_big_stride(orbref, cuda):
+    """cap = 8256 as the stride of two small frames: the replay keeps its assignments in the output
+    row in global memory (rescans included: frame 0 is the claim chain)."""
+    frames, pcap, th, nnratio = _big_stride_frames(orbref)
+    nm, match = _device_batch(cuda, frames, BIG_CAP, pcap, th, nnratio)
+    for b, (k, d, u, c, g, p, pd) in enumerate(frames):
+        wn, wm = orbref.search_by_projection(k, d, u, c, g, SCALE, p, pd, th, nnratio)
+        assert int(nm[b]) == wn
+        assert np.array_equal(match[b, :len(k)], wm)

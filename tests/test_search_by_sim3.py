@@ -23,7 +23,7 @@ F32 = np.float32
 TH = 7.5                      # LoopClosing::ComputeSim3's th
 TH_HIGH = 100
 INT_MAX = 2 ** 31 - 1
-K_SUB = 4                     # lanes per MapPoint in k_s3_points (csrc/orbx_proj.hip kSub)
+K_SUB = 4                     # lanes per MapPoint in k_s3_points' walk_window (csrc/orbx_proj.hip kSub)
 EYE_T = np.hstack([np.eye(3), np.zeros((3, 1))]).astype(np.float32)
 
 
