@@ -696,6 +696,89 @@ orbx_status orbm_triangulate(int device, const orbx_keypoint* kps1, const orbx_k
                              int* status, orbm_map_point* new_pts, orbm_observation* new_obs,
                              orbm_observation* new_ref, int* new_idx1, int* nnew, uint8_t* mark1, uint8_t* mark2);
 
+/* ---- Local map: Tracking::UpdateLocalMap and the first loop of SearchLocalPoints ----
+ * src/Tracking.cc:1283-1391 (UpdateLocalKeyFrames), :1257-1280 (UpdateLocalPoints) and :1198-1214 with the test at
+ * :1222, the step of Tracking::TrackLocalMap (:982-992) in front of orbm_frustum_batch_device and
+ * orbm_search_by_projection_device.  From a tracked frame's MapPoints it builds mvpLocalKeyFrames, mpReferenceKF and
+ * mvpLocalMapPoints and gathers the latter as the d_pts / d_npts / pcap of orbm_frustum_batch_device and the d_pdesc /
+ * d_claimed of orbm_search_by_projection_device: the three calls chain on one stream with no host copy.  All integers.
+ *
+ * KeyFrame table, nkf slots at stride cap (the layout of the calls above): d_counts[nkf]; d_kf_mp[f * cap + i] =
+ * GetMapPointMatches()[i] as a MapPoint index or -1; d_kf_bad[f] = isBad(); d_kf_rank[f] = the KeyFrame's position in
+ * the caller's std::map<KeyFrame*, ...> order, a permutation of 0..nkf-1 (NULL = slot order, as in
+ * orbm_triangulate_device); d_covis[f * 10 ..] = GetBestCovisibilityKeyFrames(10) padded with -1 (as in
+ * orbv_db_detect_loop); d_child[d_child_ptr[f] .. d_child_ptr[f + 1]) = GetChilds() in the caller's std::set order;
+ * d_parent[f] = GetParent() or -1.
+ * MapPoint table, nmp points: d_pts (flags bit 0 = !isBad(), bit 1 = Observations() > 0), d_pdesc[nmp * 32], and
+ * d_obs_ptr / d_obs as in orbm_refresh_map_points_device (only .kf is read).
+ * Frames, nframes at stride fcap: d_fcounts[fr]; d_frame_mp[fr * fcap + i] = mCurrentFrame.mvpMapPoints[i] or -1, in
+ * and out; d_frame_outlier[fr * fcap + i] (NULL = none) = the MapPoint TrackReferenceKeyFrame / TrackWithMotionModel
+ * discarded at feature i of this frame (they set its mnLastFrameSeen, :842, :965), or -1.
+ *
+ * Per frame, as the reference does it:
+ *  1 every frame MapPoint that is not bad adds a vote to each KeyFrame of its observation list, bad KeyFrames
+ *    included; a bad one is written back as -1 in d_frame_mp (:1286-1303);
+ *  2 with no vote at all the reference returns (:1305): d_local_kf[fr * kfcap ..], d_nlocal_kf[fr] and d_ref_kf[fr]
+ *    are in and out, hold the previous list and reference KeyFrame on entry and keep them then; otherwise the list
+ *    is overwritten;
+ *  3 in rank order every voted KeyFrame that is not bad joins the list; pKFmax is the first in rank order with the
+ *    most votes (:1315-1330);
+ *  4 the expansion runs over those first-stage entries only and stops at the head of an iteration once the list
+ *    holds more than 80: per KeyFrame the first covisible that is not bad and not listed, then the first such child,
+ *    then the parent if not listed -- whether or not it is bad -- which ends the whole loop (:1334-1384);
+ *  5 d_ref_kf[fr] = pKFmax, left as it was when every voted KeyFrame was bad (:1386);
+ *  6 over the local KeyFrames in list order and their features in index order, every MapPoint that is not bad is
+ *    listed at its first occurrence (:1257-1280);
+ *  7 a listed MapPoint that is in the frame's cleaned d_frame_mp or in d_frame_outlier gets flags bit 0 clear
+ *    (mnLastFrameSeen == mnId, :1222), every other one set.
+ * Outputs per frame: d_local_mp[fr * pcap + k] the MapPoint indices in list order, d_nlocal[fr] their number (at most
+ * pcap), d_out_pts[fr * pcap + k] the table's orbm_map_point with flags = (bit 0 of step 7) | (flags & 2),
+ * d_out_pdesc[(fr * pcap + k) * 32] its descriptor, d_claimed[fr * fcap + i] = d_frame_mp[i] >= 0 &&
+ * Observations() > 0 after step 1, and d_status[fr]: 0 faithful, else a mask of ORBM_LOCAL_MAP_KF_TRUNCATED (the
+ * reference's list is longer than kfcap; its first kfcap entries are kept and steps 6-7 use those),
+ * ORBM_LOCAL_MAP_POINTS_TRUNCATED (more than pcap MapPoints; the first pcap are written) and ORBM_LOCAL_MAP_INVALID.
+ * Invalid: an index the frame reads lies outside its table -- d_fcounts[fr] outside [0, fcap]; a d_frame_mp or
+ * d_frame_outlier entry outside [-1, nmp); an observation list of a voting MapPoint that does not ascend from >= 0 or
+ * is longer than ORBM_MAX_OBSERVATIONS, or an observation's kf outside [0, nkf); d_kf_rank no permutation; of a
+ * KeyFrame the expansion visits a covisible outside [-1, nkf), a child list that does not ascend from >= 0, a child
+ * outside [0, nkf) (all its children are checked) or a parent outside [-1, nkf); with no vote d_nlocal_kf[fr] outside
+ * [0, kfcap] or a previous entry outside [0, nkf); of a local KeyFrame a count outside [0, cap] or a d_kf_mp entry
+ * outside [-1, nmp).  Each is checked before the read it guards, and of an invalid frame nothing but d_status[fr] is
+ * written.  Entries at and past the counts keep their bits.
+ *
+ * d_work: orbm_local_map_work_bytes(nkf, nmp, nframes, kfcap) bytes of device memory, 4-byte aligned, that the caller
+ * zeroes once; every call leaves it zeroed again (the entries it touched are put back, so the cost follows the local
+ * map, not the whole map) and the calls allocate nothing.  One scratch serves one call at a time.  Vote counters live
+ * in LDS up to nkf = ORBM_LOCAL_MAP_LDS_KEYFRAMES and in the scratch beyond.
+ * Limits: cap, fcap <= ORBM_MAX_FEATURES, nkf <= ORBV_DB_MAX_KEYFRAMES, kfcap * cap <= INT_MAX (list positions are
+ * compared as ints); ORBX_EINVAL otherwise.  Asynchronous on `stream`. */
+enum { ORBM_LOCAL_MAP_KF_TRUNCATED = 1, ORBM_LOCAL_MAP_POINTS_TRUNCATED = 2, ORBM_LOCAL_MAP_INVALID = 4 };
+#define ORBM_LOCAL_MAP_LDS_KEYFRAMES 8192
+
+/* Pure host code, no device: the scratch size of one call; 0 for arguments the call itself refuses. */
+size_t orbm_local_map_work_bytes(int nkf, int nmp, int nframes, int kfcap);
+
+orbx_status orbm_local_map_device(const int* d_counts, const int* d_kf_mp, const uint8_t* d_kf_bad,
+                                  const int* d_kf_rank, const int* d_covis, const int* d_child_ptr,
+                                  const int* d_child, const int* d_parent, int nkf, int cap,
+                                  const orbm_map_point* d_pts, const uint8_t* d_pdesc, const int* d_obs_ptr,
+                                  const orbm_observation* d_obs, int nmp, const int* d_fcounts, int* d_frame_mp,
+                                  const int* d_frame_outlier, int nframes, int fcap, int* d_local_kf,
+                                  int* d_nlocal_kf, int kfcap, int* d_ref_kf, int* d_local_mp, int* d_nlocal,
+                                  orbm_map_point* d_out_pts, uint8_t* d_out_pdesc, int pcap, uint8_t* d_claimed,
+                                  int* d_status, void* d_work, size_t work_bytes, void* stream);
+
+/* One frame of n features, host arrays, on HIP device `device`; synchronous.  frame_mp (n) and claimed (n), local_kf
+ * (kfcap) with *nlocal_kf and *ref_kf in and out, local_mp / out_pts / out_pdesc with room for pcap points; what the
+ * device form leaves untouched keeps its bits here too.  ORBX_EINVAL when child_ptr or obs_ptr does not ascend from
+ * >= 0.  The scratch is the call's own. */
+orbx_status orbm_local_map(int device, const int* counts, const int* kf_mp, const uint8_t* kf_bad, const int* kf_rank,
+                           const int* covis, const int* child_ptr, const int* child, const int* parent, int nkf,
+                           int cap, const orbm_map_point* pts, const uint8_t* pdesc, const int* obs_ptr,
+                           const orbm_observation* obs, int nmp, int n, int* frame_mp, const int* frame_outlier,
+                           int* local_kf, int* nlocal_kf, int kfcap, int* ref_kf, int* local_mp, int* nlocal,
+                           orbm_map_point* out_pts, uint8_t* out_pdesc, int pcap, uint8_t* claimed, int* status);
+
 /* ---- DBoW2 vocabulary (TemplatedVocabulary, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h) ----
  * Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:521-528, src/KeyFrame.cc:59-66) call
  * transform(descriptors, mBowVec, mFeatVec, 4); the FeatureVector it produces is the

@@ -187,4 +187,13 @@ void launch_search_by_sim3(const orbx_keypoint* kps, const uint8_t* desc, const 
                            const uint8_t* already2, int npairs, const orbm_pose_params& P, void* scratch, int* match12,
                            int* nfound, int* match1, int* match2, hipStream_t s);
 
+// The caller's scratch of orbm_local_map_device (orbx_localmap.hip), offsets and strides in ints: the rank table
+// [nkf], then per frame a header (8), the KeyFrame list [kfcap] and the entries per KeyFrame [kfcap] -- small, and
+// cleared by one memset per call (small_bytes) -- then per frame the vote counters [nkf], the first-occurrence keys
+// [nmp] and the frame's MapPoint bitmap [(nmp + 31) / 32], which the kernels put back to zero entry by entry.
+struct LmLayout {
+    size_t inv, hdr, hstride, big, bstride, small_bytes, bytes;
+};
+LmLayout lm_layout(int nkf, int nmp, int nframes, int kfcap);
+
 }  // namespace orbx

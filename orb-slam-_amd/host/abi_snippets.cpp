@@ -209,6 +209,35 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
                                    cap, d_Tcw, d_kf_bad, d_obs_ptr, d_new_obs, d_new_ref, match_stride, 2, &P,
                                    d_new_pts, d_pdesc_rw, d_best, stream);
 
+    // Tracking::TrackLocalMap: UpdateLocalMap -> isInFrustum -> SearchByProjection on one stream
+    const int *d_kf_mp = nullptr, *d_covis = nullptr, *d_child_ptr = nullptr, *d_child = nullptr, *d_parent = nullptr;
+    const int *d_fcounts = nullptr, *d_frame_outlier = nullptr;
+    int *d_frame_mp = nullptr, *d_local_kf = nullptr, *d_nlocal_kf = nullptr, *d_ref_kf = nullptr;
+    int *d_local_mp = nullptr, *d_nlocal = nullptr, *d_lm_status = nullptr;
+    orbm_map_point* d_local_pts = nullptr;
+    uint8_t *d_local_pdesc = nullptr, *d_local_claimed = nullptr;
+    void* d_work = nullptr;   // hipMalloc + hipMemset once; every call leaves it zeroed
+    int nmp = 100000, kfcap = 96;
+    size_t work_bytes = orbm_local_map_work_bytes(nkf, nmp, nframes, kfcap);
+    orbm_local_map_device(d_counts, d_kf_mp, d_kf_bad, d_rank, d_covis, d_child_ptr, d_child, d_parent, nkf, cap,
+                          d_mps_rw, d_pdesc_rw, d_obs_ptr, d_obs, nmp, d_fcounts, d_frame_mp, d_frame_outlier, nframes,
+                          cap, d_local_kf, d_nlocal_kf, kfcap, d_ref_kf, d_local_mp, d_nlocal, d_local_pts,
+                          d_local_pdesc, pcap, d_local_claimed, d_lm_status, d_work, work_bytes, stream);
+    orbm_frustum_batch_device(d_local_pts, d_nlocal, nframes, pcap, d_Tcw, &P, 0.5f, d_pts, d_ntomatch, stream);
+    orbm_search_by_projection_device(d_kps_un, d_desc, d_uright, d_local_claimed, d_fcounts, nframes, cap, d_pts,
+                                     d_local_pdesc, d_nlocal, pcap, &prm, d_match, d_nmatches, stream);
+    // ... and one frame on host arrays
+    std::vector<int> kf_mp((size_t)nkf * cap, -1), kf_covis((size_t)nkf * 10, -1), child_ptr(nkf + 1), child;
+    std::vector<int> parent(nkf, -1), frame_mp(n, -1), local_kf(kfcap), local_mp(pcap);
+    std::vector<orbm_map_point> local_pts(pcap);
+    std::vector<uint8_t> local_pdesc((size_t)pcap * 32), local_claimed(n);
+    int nlocal_kf = 0, ref_kf = -1, nlocal = 0, lm_status = 0;
+    orbm_local_map(0, tcounts.data(), kf_mp.data(), kf_bad.data(), nullptr, kf_covis.data(), child_ptr.data(),
+                   child.data(), parent.data(), nkf, cap, mps.data(), pdesc.data(), obs_ptr.data(), obs.data(), np, n,
+                   frame_mp.data(), nullptr, local_kf.data(), &nlocal_kf, kfcap, &ref_kf, local_mp.data(), &nlocal,
+                   local_pts.data(), local_pdesc.data(), pcap, local_claimed.data(), &lm_status);
+    if (lm_status & ORBM_LOCAL_MAP_INVALID) nlocal = 0;
+
     // ComputeBoW
     std::vector<int32_t> bw(n), node(n), ptr(n + 1), idx(n);
     std::vector<double> bv(n);

@@ -49,6 +49,7 @@ EXPORTED = [
     "orbx_undistort_points", "orbx_image_bounds", "orbx_undistort_batch_device", "orbx_rgbd_stereo_batch_device",
     "orbx_rgbd_stereo", "orbm_frustum_batch_device", "orbm_frustum",
     "orbm_refresh_map_points_device", "orbm_refresh_map_points", "orbm_triangulate_device", "orbm_triangulate",
+    "orbm_local_map_work_bytes", "orbm_local_map_device", "orbm_local_map",
     "orbm_best2_csr_device", "orbm_best2_csr", "orbm_stereo_band", "orbm_stereo_band_device",
     "orbv_load_text", "orbv_create", "orbv_destroy", "orbv_info", "orbv_transform", "orbv_transform_batch_device",
     "orbv_score", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_batch_device", "orbv_db_erase",
@@ -270,6 +271,14 @@ def _load():
                                           P(PoseParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_triangulate.argtypes = [C.c_int, vp, vp, f32p, f32p, C.c_int, f32p, vp, vp, f32p, f32p, C.c_int, f32p, i32p,
                                    P(PoseParams), f32p, i32p, vp, vp, vp, i32p, i32p, u8p, u8p]
+    L.orbm_local_map_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.orbm_local_map_work_bytes.restype = C.c_size_t
+    L.orbm_local_map_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp,
+                                        vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp,
+                                        vp, vp, C.c_size_t, vp]
+    L.orbm_local_map.argtypes = [C.c_int, i32p, i32p, u8p, i32p, i32p, i32p, i32p, i32p, C.c_int, C.c_int, vp, u8p,
+                                 i32p, vp, C.c_int, C.c_int, i32p, i32p, i32p, i32p, C.c_int, i32p, i32p, i32p, vp,
+                                 u8p, C.c_int, u8p, i32p]
     L.orbm_best2_csr_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     L.orbm_best2_csr.argtypes = [C.c_int, u8p, C.c_int, u8p, C.c_int, i32p, i32p, C.c_int, i32p, i32p, i32p]
     L.orbm_stereo_band.argtypes = [C.c_int, vp, u8p, C.c_int, vp, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_float,
@@ -764,6 +773,111 @@ def triangulate(kps1, pose1, kps2, pose2, match, params, kps1_raw=None, kps2_raw
     k = nnew.value
     return dict(x3d=x[:n1], status=status[:n1], new_pts=pts[:k].copy(), new_obs=obs[:k].copy(), new_ref=ref[:k].copy(),
                 new_idx1=idx1[:k].copy(), nnew=k, mark1=mk1, mark2=mk2)
+
+
+# d_status bits of orbm_local_map_device (include/orbx.h) and the KeyFrame count up to which votes are counted in LDS
+LOCAL_MAP_KF_TRUNCATED, LOCAL_MAP_POINTS_TRUNCATED, LOCAL_MAP_INVALID = 1, 2, 4
+LOCAL_MAP_LDS_KEYFRAMES = 8192
+
+
+def local_map_work_bytes(nkf, nmp, nframes, kfcap):
+    """orbm_local_map_work_bytes: the scratch one local_map_device call is handed (0 for sizes the call refuses)."""
+    return int(lib.orbm_local_map_work_bytes(int(nkf), int(nmp), int(nframes), int(kfcap)))
+
+
+def local_map_work(nkf, nmp, nframes, kfcap, device):
+    """A zeroed scratch tensor for local_map_device; every call leaves it zeroed, so it is made once."""
+    import torch
+    nbytes = local_map_work_bytes(nkf, nmp, nframes, kfcap)
+    if nbytes == 0:
+        raise ValueError("local_map_work: sizes out of range")
+    return torch.zeros(((nbytes + 3) // 4,), dtype=torch.int32, device=device)
+
+
+def local_map_device(counts, kf_mp, kf_bad, covis, child_ptr, child, parent, pts, pdesc, obs_ptr, obs, fcounts,
+                     frame_mp, local_kf, nlocal_kf, ref_kf, pcap, work, kf_rank=None, frame_outlier=None, out=None,
+                     stream=None):
+    """Tracking::UpdateLocalMap and the first loop of SearchLocalPoints over device tensors (include/orbx.h).
+    KeyFrame table: counts (nkf,), kf_mp (nkf, cap) int32 MapPoint indices or -1, kf_bad (nkf,) uint8, covis
+    (nkf, 10) int32 padded with -1, child_ptr (nkf + 1,) / child int32, parent (nkf,) int32, kf_rank (nkf,) int32 or
+    None = slot order.  MapPoint table: pts (nmp, 12) int32 view of MAP_POINT_DTYPE, pdesc (nmp, 32) uint8, obs_ptr
+    (nmp + 1,), obs (nobs, 2) int32.  Frames: fcounts (B,), frame_mp (B, fcap) int32 (bad MapPoints are nulled in
+    place), frame_outlier (B, fcap) int32 or None.  local_kf (B, kfcap) int32, nlocal_kf (B,) and ref_kf (B,) hold
+    the previous list and reference KeyFrame and are updated in place.  work: local_map_work(...).  out: a dict of
+    preallocated outputs (any subset).  Returns a dict of tensors: local_mp (B, pcap), nlocal (B,), out_pts
+    (B, pcap, 12) and out_pdesc (B, pcap, 32) -- the pts / npts of frustum_batch_device and the pdesc of the
+    projection search -- claimed (B, fcap) uint8 and status (B,) (LOCAL_MAP_* bits, 0 = faithful)."""
+    import torch
+    nkf, cap = kf_mp.shape[0], kf_mp.shape[1]
+    nmp = obs_ptr.shape[0] - 1
+    B, fcap = frame_mp.shape[0], frame_mp.shape[1]
+    kfcap = local_kf.shape[1]
+    out = dict(out or {})
+    dev = frame_mp.device
+    shapes = dict(local_mp=((B, pcap), torch.int32), nlocal=((B,), torch.int32),
+                  out_pts=((B, pcap, 12), torch.int32), out_pdesc=((B, pcap, 32), torch.uint8),
+                  claimed=((B, fcap), torch.uint8), status=((B,), torch.int32))
+    for k, (shape, dt) in shapes.items():
+        if out.get(k) is None:
+            out[k] = torch.zeros(shape, dtype=dt, device=dev)
+        elif tuple(out[k].shape) != shape or out[k].dtype != dt or not out[k].is_contiguous():
+            raise ValueError("local_map_device: out[%r] must be a contiguous %s tensor of shape %s" % (k, dt, shape))
+    _check("orbm_local_map_device",
+           lib.orbm_local_map_device(_ptr(counts), _ptr(kf_mp), _ptr(kf_bad), _ptr(kf_rank), _ptr(covis),
+                                     _ptr(child_ptr), _ptr(child), _ptr(parent), nkf, cap, _ptr(pts), _ptr(pdesc),
+                                     _ptr(obs_ptr), _ptr(obs), nmp, _ptr(fcounts), _ptr(frame_mp),
+                                     _ptr(frame_outlier), B, fcap, _ptr(local_kf), _ptr(nlocal_kf), kfcap,
+                                     _ptr(ref_kf), _ptr(out["local_mp"]), _ptr(out["nlocal"]), _ptr(out["out_pts"]),
+                                     _ptr(out["out_pdesc"]), int(pcap), _ptr(out["claimed"]), _ptr(out["status"]),
+                                     _ptr(work), work.numel() * work.element_size(), _stream(stream)))
+    return out
+
+
+def local_map(counts, kf_mp, kf_bad, covis, child_ptr, child, parent, pts, pdesc, obs_ptr, obs, frame_mp, local_kf,
+              ref_kf, kfcap, pcap, kf_rank=None, frame_outlier=None, out=None, device=0):
+    """The same for one frame on host arrays: frame_mp (n,) int32, local_kf the previous list (any length <= kfcap),
+    ref_kf the previous reference KeyFrame.  out: optional dict of local_kf (kfcap,), local_mp (pcap,), out_pts
+    (pcap,) MAP_POINT_DTYPE, out_pdesc (pcap, 32) and claimed (n,) whose contents stand where the call writes
+    nothing.  Returns a dict: frame_mp (the cleaned copy), local_kf (kfcap,), nlocal_kf, ref_kf, local_mp, nlocal,
+    out_pts, out_pdesc, claimed, status."""
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)
+    cn, km, bad = i32(counts), i32(kf_mp), np.ascontiguousarray(kf_bad, np.uint8)
+    nkf, cap = (km.shape[0], km.shape[1]) if km.ndim == 2 else (0, 1)
+    cv, cp, ch, pa = i32(covis).reshape(-1), i32(child_ptr), i32(child).reshape(-1), i32(parent)
+    p = np.ascontiguousarray(pts, MAP_POINT_DTYPE).reshape(-1)
+    pd = np.ascontiguousarray(pdesc, np.uint8).reshape(-1, 32)
+    op, ob = i32(obs_ptr), np.ascontiguousarray(obs, OBSERVATION_DTYPE).reshape(-1)
+    nmp = len(op) - 1
+    fm = np.array(frame_mp, np.int32).reshape(-1)
+    n = len(fm)
+    rk = None if kf_rank is None else i32(kf_rank)
+    fo = None if frame_outlier is None else i32(frame_outlier).reshape(-1)
+    prev = i32(local_kf).reshape(-1)
+    if not (len(cn) == len(bad) == len(pa) == nkf and len(cv) == 10 * nkf and len(cp) == nkf + 1 and
+            len(p) == len(pd) == nmp and (rk is None or len(rk) == nkf) and (fo is None or len(fo) == n) and
+            len(prev) <= kfcap):
+        raise ValueError("local_map: array sizes disagree")
+    out = dict(out or {})
+    lk = np.array(out["local_kf"], np.int32) if out.get("local_kf") is not None else np.zeros(kfcap, np.int32)
+    lk[:len(prev)] = prev
+    lm = np.array(out["local_mp"], np.int32) if out.get("local_mp") is not None else np.zeros(pcap, np.int32)
+    opt = (np.array(out["out_pts"], MAP_POINT_DTYPE) if out.get("out_pts") is not None
+           else np.zeros(pcap, MAP_POINT_DTYPE))
+    opd = (np.array(out["out_pdesc"], np.uint8).reshape(-1, 32) if out.get("out_pdesc") is not None
+           else np.zeros((pcap, 32), np.uint8))
+    cl = np.array(out["claimed"], np.uint8) if out.get("claimed") is not None else np.zeros(max(n, 1), np.uint8)
+    if not (len(lk) == kfcap and len(lm) == len(opt) == len(opd) == pcap and len(cl) >= n):
+        raise ValueError("local_map: out array sizes disagree")
+    nlk, ref, nl, st = C.c_int(len(prev)), C.c_int(int(ref_kf)), C.c_int(0), C.c_int(0)
+    ip = lambda a: None if a is None or a.size == 0 else _i32p(a)
+    _check("orbm_local_map",
+           lib.orbm_local_map(device, ip(cn), ip(km), _u8(bad) if nkf else None, ip(rk), ip(cv), _i32p(cp), ip(ch),
+                              ip(pa), nkf, cap, p.ctypes.data if nmp else None, _u8(pd) if nmp else None, _i32p(op),
+                              ob.ctypes.data if ob.size else None, nmp, n, ip(fm), ip(fo), _i32p(lk), C.byref(nlk),
+                              kfcap, C.byref(ref), _i32p(lm), C.byref(nl), opt.ctypes.data, _u8(opd), pcap, _u8(cl),
+                              C.byref(st)))
+    return dict(frame_mp=fm, local_kf=lk, nlocal_kf=nlk.value, ref_kf=ref.value, local_mp=lm, nlocal=nl.value,
+                out_pts=opt, out_pdesc=opd, claimed=cl[:n], status=st.value)
 
 
 TIE_FIRST, TIE_LAST = 0, 1
