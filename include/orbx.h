@@ -779,6 +779,133 @@ orbx_status orbm_local_map(int device, const int* counts, const int* kf_mp, cons
                            int* local_kf, int* nlocal_kf, int kfcap, int* ref_kf, int* local_mp, int* nlocal,
                            orbm_map_point* out_pts, uint8_t* out_pdesc, int pcap, uint8_t* claimed, int* status);
 
+/* ---- The covisibility graph: KeyFrame::UpdateConnections and what hangs on it ----
+ * src/KeyFrame.cc:289-379 (UpdateConnections) with AddConnection (:123-136) and UpdateBestCovisibles (:138-157), the
+ * connection part of SetBadFlag (:466-467, :476-477) with EraseConnection (:553-567), and the getters
+ * GetBestCovisibilityKeyFrames (:174-182), GetConnectedKeyFrames (:159-166), GetCovisiblesByWeight (:184-199) and
+ * GetChilds.  The graph lives in caller-owned device memory beside the KeyFrame and MapPoint tables of
+ * orbm_local_map_device, is updated in place from the observation lists the refresh and the triangulation keep
+ * current, and the getters write the d_covis / d_child_ptr / d_child / d_connected tables orbm_local_map_device and
+ * orbv_db_detect_*_device take: the calls chain on one stream with no host copy.  All integers.
+ *
+ * nkf slots at row stride ccap <= ORBM_MAX_CONNECTIONS; all arrays are read and written in place, and entries at and
+ * past the counts keep their bits. */
+typedef struct {
+    int32_t* conn_kf;   /* [nkf * ccap] mConnectedKeyFrameWeights of slot f at f * ccap: the KeyFrames, every voted one
+                           (also below the threshold, :367), in ascending slot order, none twice */
+    int32_t* conn_w;    /* [nkf * ccap] their weights */
+    int32_t* nconn;     /* [nkf] the map's size */
+    int32_t* ord_kf;    /* [nkf * ccap] mvpOrderedConnectedKeyFrames: descending weight, among equal weights descending
+                           d_kf_rank (the reference sorts ascending on (weight, pointer) and pushes to the front,
+                           :146-156, :354-361) */
+    int32_t* ord_w;     /* [nkf * ccap] mvOrderedWeights */
+    int32_t* nord;      /* [nkf] their length */
+    int32_t* parent;    /* [nkf] mpParent or -1 */
+    uint8_t* first;     /* [nkf] mbFirstConnection */
+} orbm_covis_graph;
+
+#define ORBM_MAX_CONNECTIONS 4096
+
+/* KeyFrame::UpdateConnections for d_targets[0 .. ntargets) as if called one after another in that order (a slot may
+ * repeat; the targets run as launches in sequence on `stream`, and no result is read on the host).  `graph` is a host
+ * struct of device pointers.  The KeyFrame table (d_counts, d_kf_mp at stride cap, d_kf_rank or NULL = slot order) and
+ * the MapPoint table (d_pts, d_obs_ptr, d_obs, nmp) are those of orbm_local_map_device; of an orbm_map_point only
+ * flags bit 0 is read, of an observation only .kf.  th >= 1 is the reference's 15 (:330); root is the slot whose
+ * mnId is 0, or -1.
+ *
+ * Per target t, as the reference does it:
+ *  1 every MapPoint of t that is not NULL and not bad adds a vote to each KeyFrame of its observation list but t
+ *    itself (slot equality stands for mnId==mnId, :316); a bad KeyFrame is counted, isBad() is not asked (:302-320);
+ *  2 with no vote at all the reference returns (:323): nothing of the graph is written, d_status = ORBM_CONN_EMPTY;
+ *  3 over the voted KeyFrames in ascending rank pKFmax is the first with the strictly largest count; every KeyFrame
+ *    with count >= th enters vPairs and receives AddConnection(t, count); if none does, pKFmax alone (:328-352);
+ *  4 AddConnection(n <- t, w) (:123-136) inserts t into n's map, or overwrites a different weight; with an equal
+ *    weight nothing changes and n's ordered list is NOT rebuilt; after an insert or overwrite UpdateBestCovisibles
+ *    (:138-157) rebuilds n's ordered list from its WHOLE map, entries below th included;
+ *  5 t's map becomes all voted KeyFrames with their counts, its ordered list vPairs only (:354-369); a KeyFrame t was
+ *    connected to before and no longer votes for keeps its stale entry for t -- the reference erases nothing here;
+ *  6 if first[t] is set and t != root: parent[t] = ord_kf[t][0], first[t] = 0 (:371-376); otherwise both stand.
+ *
+ * d_status[i], per position in d_targets: 0 faithful; ORBM_CONN_EMPTY (step 2); ORBM_CONN_NOSPC: t's map, or the map
+ * of a neighbour that needs an insert, would exceed ccap; ORBM_CONN_INVALID: the reference would read out of bounds --
+ * the target outside [0, nkf); d_counts[t] outside [0, cap]; a d_kf_mp entry outside [-1, nmp); an observation list of
+ * a voting MapPoint that does not ascend from >= 0 or is longer than ORBM_MAX_OBSERVATIONS; an observation's kf
+ * outside [0, nkf); d_kf_rank no permutation; of a row the call reads -- the map row of every vPairs neighbour -- nconn
+ * outside [0, ccap] or an entry outside [0, nkf).  When t's own map exceeds ccap the neighbours' rows are not read;
+ * otherwise an invalid neighbour row outranks a full one.  Each read is checked before it is made, and the status is
+ * decided before the first write: for NOSPC and INVALID nothing but d_status[i] is written, neighbour rows included.
+ * Later targets still run.  What keeps its bits: every row and count of a KeyFrame that is neither t nor a neighbour
+ * that received an insert or overwrite, row entries at and past the new counts, parent / first unless step 6 applies.
+ *
+ * d_work: orbm_connections_work_bytes(nkf, ccap) bytes of device memory, 4-byte aligned, that the caller zeroes once;
+ * every call leaves it zeroed again and the calls allocate nothing.  One scratch serves one call at a time.  Vote
+ * counters live in LDS up to nkf = ORBM_LOCAL_MAP_LDS_KEYFRAMES and in the scratch beyond.
+ * Limits: nkf <= ORBV_DB_MAX_KEYFRAMES, cap <= ORBM_MAX_FEATURES, 1 <= ccap <= ORBM_MAX_CONNECTIONS, th >= 1, root in
+ * [-1, nkf); ORBX_EINVAL otherwise.  Asynchronous on `stream`. */
+enum { ORBM_CONN_EMPTY = 1, ORBM_CONN_NOSPC = 2, ORBM_CONN_INVALID = 4 };
+
+/* Pure host code, no device: the scratch size of one call; 0 for arguments the call itself refuses. */
+size_t orbm_connections_work_bytes(int nkf, int ccap);
+
+orbx_status orbm_update_connections_device(const orbm_covis_graph* graph, int nkf, int ccap, const int* d_counts,
+                                           const int* d_kf_mp, int cap, const int* d_kf_rank,
+                                           const orbm_map_point* d_pts, const int* d_obs_ptr,
+                                           const orbm_observation* d_obs, int nmp, const int* d_targets, int ntargets,
+                                           int th, int root, int* d_status, void* d_work, size_t work_bytes,
+                                           void* stream);
+
+/* The same on host arrays (`graph` holds host pointers, read and written in place), on HIP device `device`;
+ * synchronous.  The argument checks run before any device call.  ORBX_EINVAL also when obs_ptr does not ascend from
+ * >= 0 or nkf < 1.  What the device form leaves untouched keeps its bits here too.  The scratch is the call's own. */
+orbx_status orbm_update_connections(int device, const orbm_covis_graph* graph, int nkf, int ccap, const int* counts,
+                                    const int* kf_mp, int cap, const int* kf_rank, const orbm_map_point* pts,
+                                    const int* obs_ptr, const orbm_observation* obs, int nmp, const int* targets,
+                                    int ntargets, int th, int root, int* status);
+
+/* The connection part of KeyFrame::SetBadFlag (:466-467, :476-477) for d_targets in sequence: for every n in t's map,
+ * EraseConnection (:553-567) -- if n's map holds t, t is removed (the row closes up) and n's ordered list is rebuilt
+ * from its whole map; otherwise n is left alone -- then nconn[t] = nord[t] = 0; t's row entries keep their bits.  An
+ * entry of t's map that names t itself is skipped.  d_status[i]: 0, or ORBM_CONN_INVALID when the target is outside
+ * [0, nkf), d_kf_rank is no permutation, nconn[t] is outside [0, ccap], an entry of t's row is outside [0, nkf), or
+ * the row of one of them has such a count or entry; checked before the reads they guard, and then nothing but
+ * d_status[i] is written.  The mbNotErase test, the observation erasure, the spanning-tree repair (:480-537) and the
+ * database erase stay with the caller.  d_work as above.  Asynchronous on `stream`. */
+orbx_status orbm_erase_connections_device(const orbm_covis_graph* graph, int nkf, int ccap, const int* d_kf_rank,
+                                          const int* d_targets, int ntargets, int* d_status, void* d_work,
+                                          size_t work_bytes, void* stream);
+
+/* The getters, asynchronous on `stream`; a nord / nconn outside [0, ccap] is clamped into it before the row is read.
+ * d_out[f * N + j] = GetBestCovisibilityKeyFrames(N)[j] of every slot, padded with -1 (:174-182): with N = 10 the
+ * d_covis of orbm_local_map_device and orbv_db_detect_*_device.  1 <= N <= ORBM_MAX_CONNECTIONS. */
+orbx_status orbm_best_covisibles_device(const orbm_covis_graph* graph, int nkf, int ccap, int N, int* d_out,
+                                        void* stream);
+
+/* d_mask[nkf] = 1 where the slot is in GetConnectedKeyFrames() of t (:159-166), else 0: the d_connected of
+ * orbv_db_detect_loop_device.  A map entry outside [0, nkf) marks nothing.  t in [0, nkf). */
+orbx_status orbm_connected_mask_device(const orbm_covis_graph* graph, int nkf, int ccap, int t, uint8_t* d_mask,
+                                       void* stream);
+
+/* d_n[f] = the length GetCovisiblesByWeight(w) returns (:184-199): the index of the first ordered weight < w, and 0
+ * when there is none -- upper_bound hits end() when every weight is >= w, and the reference returns an empty vector
+ * then (:192).  The list is d_ord_kf[f * ccap .. + d_n[f]). */
+orbx_status orbm_covisibles_by_weight_device(const orbm_covis_graph* graph, int nkf, int ccap, int w, int* d_n,
+                                             void* stream);
+
+/* GetChilds() of every slot as the CSR orbm_local_map_device reads: d_child[d_child_ptr[f] .. d_child_ptr[f + 1]) =
+ * {c : d_parent[c] == f and not d_kf_bad[c]} in ascending d_kf_rank (NULL = slot order), the std::set<KeyFrame*>
+ * order; d_child_ptr has nkf + 1 entries, d_child room for nkf.  This equals mspChildrens for every KeyFrame that is
+ * not bad: AddChild is called where the parent is set (:374, :397) and EraseChild only by a KeyFrame turning bad
+ * (:537); a bad KeyFrame's own set may be stale in the reference, and the local-map expansion asks it only of
+ * KeyFrames that are not bad.  *d_status (one int): 0, or ORBM_CONN_INVALID when a parent is outside [-1, nkf) or
+ * d_kf_rank is no permutation; then nothing else is written.  d_work: orbm_children_work_bytes(nkf) bytes, zeroed
+ * once by the caller and left zeroed by every call.  A child's place is found by counting its siblings of lower
+ * rank: the cost grows with the square of a KeyFrame's children.  Asynchronous on `stream`. */
+size_t orbm_children_work_bytes(int nkf);
+
+orbx_status orbm_children_device(const int* d_parent, const uint8_t* d_kf_bad, const int* d_kf_rank, int nkf,
+                                 int* d_child_ptr, int* d_child, int* d_status, void* d_work, size_t work_bytes,
+                                 void* stream);
+
 /* ---- DBoW2 vocabulary (TemplatedVocabulary, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h) ----
  * Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:521-528, src/KeyFrame.cc:59-66) call
  * transform(descriptors, mBowVec, mFeatVec, 4); the FeatureVector it produces is the

@@ -238,6 +238,35 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
                    local_pts.data(), local_pdesc.data(), pcap, local_claimed.data(), &lm_status);
     if (lm_status & ORBM_LOCAL_MAP_INVALID) nlocal = 0;
 
+    // the covisibility graph: KeyFrame::UpdateConnections after an insertion, then the tables the calls above take
+    int ccap = 256, new_kf = nkf - 1, root = 0, ntargets = 1;
+    orbm_covis_graph graph{};   // eight hipMalloc'ed arrays: nkf * ccap rows, nkf counts, parent, first (memset to 1)
+    int *d_targets = nullptr, *d_conn_status = nullptr, *d_covis_rw = nullptr, *d_child_ptr_rw = nullptr;
+    int *d_child_rw = nullptr, *d_child_status = nullptr, *d_by_weight = nullptr;
+    uint8_t* d_connected = nullptr;
+    void *d_conn_work = nullptr, *d_child_work = nullptr;   // hipMalloc + hipMemset once each
+    size_t conn_bytes = orbm_connections_work_bytes(nkf, ccap), child_bytes = orbm_children_work_bytes(nkf);
+    orbm_update_connections_device(&graph, nkf, ccap, d_counts, d_kf_mp, cap, d_rank, d_mps_rw, d_obs_ptr, d_obs, nmp,
+                                   d_targets, ntargets, /*th*/ 15, root, d_conn_status, d_conn_work, conn_bytes,
+                                   stream);
+    orbm_best_covisibles_device(&graph, nkf, ccap, 10, d_covis_rw, stream);          // d_covis
+    orbm_children_device(graph.parent, d_kf_bad, d_rank, nkf, d_child_ptr_rw, d_child_rw, d_child_status,
+                         d_child_work, child_bytes, stream);                          // d_child_ptr, d_child
+    orbm_connected_mask_device(&graph, nkf, ccap, new_kf, d_connected, stream);      // DetectLoopCandidates
+    orbm_covisibles_by_weight_device(&graph, nkf, ccap, 100, d_by_weight, stream);   // the essential graph
+    // KeyFrame::SetBadFlag's connection part
+    orbm_erase_connections_device(&graph, nkf, ccap, d_rank, d_targets, ntargets, d_conn_status, d_conn_work,
+                                  conn_bytes, stream);
+    // ... and on host arrays
+    std::vector<int> conn_kf((size_t)nkf * ccap), conn_w((size_t)nkf * ccap), ord_kf((size_t)nkf * ccap);
+    std::vector<int> ord_w((size_t)nkf * ccap), nconn(nkf), nord(nkf), conn_status(ntargets);
+    std::vector<uint8_t> first(nkf, 1);
+    orbm_covis_graph hgraph{conn_kf.data(), conn_w.data(), nconn.data(), ord_kf.data(), ord_w.data(), nord.data(),
+                            parent.data(), first.data()};
+    orbm_update_connections(0, &hgraph, nkf, ccap, tcounts.data(), kf_mp.data(), cap, nullptr, mps.data(),
+                            obs_ptr.data(), obs.data(), np, &new_kf, ntargets, 15, root, conn_status.data());
+    if (conn_status[0] == ORBM_CONN_NOSPC || conn_status[0] == ORBM_CONN_INVALID) nlocal = 0;
+
     // ComputeBoW
     std::vector<int32_t> bw(n), node(n), ptr(n + 1), idx(n);
     std::vector<double> bv(n);

@@ -50,6 +50,9 @@ EXPORTED = [
     "orbx_rgbd_stereo", "orbm_frustum_batch_device", "orbm_frustum",
     "orbm_refresh_map_points_device", "orbm_refresh_map_points", "orbm_triangulate_device", "orbm_triangulate",
     "orbm_local_map_work_bytes", "orbm_local_map_device", "orbm_local_map",
+    "orbm_connections_work_bytes", "orbm_update_connections_device", "orbm_update_connections",
+    "orbm_erase_connections_device", "orbm_best_covisibles_device", "orbm_connected_mask_device",
+    "orbm_covisibles_by_weight_device", "orbm_children_work_bytes", "orbm_children_device",
     "orbm_best2_csr_device", "orbm_best2_csr", "orbm_stereo_band", "orbm_stereo_band_device",
     "orbv_load_text", "orbv_create", "orbv_destroy", "orbv_info", "orbv_transform", "orbv_transform_batch_device",
     "orbv_score", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_batch_device", "orbv_db_erase",
@@ -171,6 +174,12 @@ def camera(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
     return Camera(fx, fy, cx, cy, k1, k2, p1, p2, k3)
 
 
+class CovisGraph(C.Structure):
+    """orbm_covis_graph: the covisibility graph's tables (host or device pointers)."""
+    _fields_ = [("conn_kf", C.c_void_p), ("conn_w", C.c_void_p), ("nconn", C.c_void_p), ("ord_kf", C.c_void_p),
+                ("ord_w", C.c_void_p), ("nord", C.c_void_p), ("parent", C.c_void_p), ("first", C.c_void_p)]
+
+
 class _Params(C.Structure):
     _fields_ = [("nfeatures", C.c_int), ("scale_factor", C.c_float), ("nlevels", C.c_int),
                 ("ini_th_fast", C.c_int), ("min_th_fast", C.c_int)]
@@ -279,6 +288,20 @@ def _load():
     L.orbm_local_map.argtypes = [C.c_int, i32p, i32p, u8p, i32p, i32p, i32p, i32p, i32p, C.c_int, C.c_int, vp, u8p,
                                  i32p, vp, C.c_int, C.c_int, i32p, i32p, i32p, i32p, C.c_int, i32p, i32p, i32p, vp,
                                  u8p, C.c_int, u8p, i32p]
+    L.orbm_connections_work_bytes.argtypes = [C.c_int, C.c_int]
+    L.orbm_connections_work_bytes.restype = C.c_size_t
+    L.orbm_update_connections_device.argtypes = [P(CovisGraph), C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp,
+                                                 C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]
+    L.orbm_update_connections.argtypes = [C.c_int, P(CovisGraph), C.c_int, C.c_int, i32p, i32p, C.c_int, i32p, vp,
+                                          i32p, vp, C.c_int, i32p, C.c_int, C.c_int, C.c_int, i32p]
+    L.orbm_erase_connections_device.argtypes = [P(CovisGraph), C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_size_t,
+                                                vp]
+    L.orbm_best_covisibles_device.argtypes = [P(CovisGraph), C.c_int, C.c_int, C.c_int, vp, vp]
+    L.orbm_connected_mask_device.argtypes = [P(CovisGraph), C.c_int, C.c_int, C.c_int, vp, vp]
+    L.orbm_covisibles_by_weight_device.argtypes = [P(CovisGraph), C.c_int, C.c_int, C.c_int, vp, vp]
+    L.orbm_children_work_bytes.argtypes = [C.c_int]
+    L.orbm_children_work_bytes.restype = C.c_size_t
+    L.orbm_children_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp]
     L.orbm_best2_csr_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     L.orbm_best2_csr.argtypes = [C.c_int, u8p, C.c_int, u8p, C.c_int, i32p, i32p, C.c_int, i32p, i32p, i32p]
     L.orbm_stereo_band.argtypes = [C.c_int, vp, u8p, C.c_int, vp, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_float,
@@ -878,6 +901,214 @@ def local_map(counts, kf_mp, kf_bad, covis, child_ptr, child, parent, pts, pdesc
                               C.byref(st)))
     return dict(frame_mp=fm, local_kf=lk, nlocal_kf=nlk.value, ref_kf=ref.value, local_mp=lm, nlocal=nl.value,
                 out_pts=opt, out_pdesc=opd, claimed=cl[:n], status=st.value)
+
+
+# d_status values of orbm_update_connections_device / orbm_erase_connections_device (include/orbx.h) and the row limit
+CONN_EMPTY, CONN_NOSPC, CONN_INVALID = 1, 2, 4
+MAX_CONNECTIONS = 4096
+_GRAPH_FIELDS = ("conn_kf", "conn_w", "nconn", "ord_kf", "ord_w", "nord", "parent", "first")
+
+
+def covis_graph(nkf, ccap, device=None):
+    """An empty covisibility graph of nkf slots at row stride ccap: a dict of conn_kf / conn_w / ord_kf / ord_w
+    (nkf, ccap) int32, nconn / nord (nkf,) int32, parent (nkf,) int32 filled with -1 and first (nkf,) uint8 filled
+    with 1 (mbFirstConnection).  Torch tensors on `device`, numpy arrays when device is None."""
+    if device is None:
+        g = {k: np.zeros((nkf, ccap), np.int32) for k in ("conn_kf", "conn_w", "ord_kf", "ord_w")}
+        g.update(nconn=np.zeros(nkf, np.int32), nord=np.zeros(nkf, np.int32), parent=np.full(nkf, -1, np.int32),
+                 first=np.ones(nkf, np.uint8))
+        return g
+    import torch
+    g = {k: torch.zeros((nkf, ccap), dtype=torch.int32, device=device) for k in ("conn_kf", "conn_w", "ord_kf", "ord_w")}
+    g.update(nconn=torch.zeros(nkf, dtype=torch.int32, device=device),
+             nord=torch.zeros(nkf, dtype=torch.int32, device=device),
+             parent=torch.full((nkf,), -1, dtype=torch.int32, device=device),
+             first=torch.ones(nkf, dtype=torch.uint8, device=device))
+    return g
+
+
+def _graph_dims(fn, g):
+    if sorted(g) != sorted(_GRAPH_FIELDS):
+        raise ValueError("%s: the graph must hold exactly %s" % (fn, ", ".join(_GRAPH_FIELDS)))
+    if g["conn_kf"].ndim != 2:
+        raise ValueError("%s: conn_kf must be (nkf, ccap)" % fn)
+    nkf, ccap = int(g["conn_kf"].shape[0]), int(g["conn_kf"].shape[1])
+    for k in _GRAPH_FIELDS:
+        want = (nkf, ccap) if k in ("conn_kf", "conn_w", "ord_kf", "ord_w") else (nkf,)
+        if tuple(g[k].shape) != want:
+            raise ValueError("%s: graph[%r] must have shape %s" % (fn, k, want))
+    return nkf, ccap
+
+
+def _graph_device(fn, g):
+    """(CovisGraph of device pointers, nkf, ccap) of a dict of contiguous torch tensors."""
+    import torch
+    nkf, ccap = _graph_dims(fn, g)
+    for k in _GRAPH_FIELDS:
+        dt = torch.uint8 if k == "first" else torch.int32
+        if g[k].dtype != dt or not g[k].is_contiguous():
+            raise ValueError("%s: graph[%r] must be a contiguous %s tensor" % (fn, k, dt))
+    return CovisGraph(*[g[k].data_ptr() for k in _GRAPH_FIELDS]), nkf, ccap
+
+
+def connections_work_bytes(nkf, ccap):
+    """orbm_connections_work_bytes: the scratch of one update / erase call (0 for sizes the calls refuse)."""
+    return int(lib.orbm_connections_work_bytes(int(nkf), int(ccap)))
+
+
+def connections_work(nkf, ccap, device):
+    """A zeroed scratch tensor for update_connections_device / erase_connections_device; every call leaves it zeroed."""
+    import torch
+    nbytes = connections_work_bytes(nkf, ccap)
+    if nbytes == 0:
+        raise ValueError("connections_work: sizes out of range")
+    return torch.zeros(((nbytes + 3) // 4,), dtype=torch.int32, device=device)
+
+
+def _work_bytes(work):
+    return work.numel() * work.element_size()
+
+
+def update_connections_device(graph, counts, kf_mp, pts, obs_ptr, obs, targets, work, th=15, root=-1, kf_rank=None,
+                              status=None, stream=None):
+    """KeyFrame::UpdateConnections for targets (int32 tensor of slots, run in sequence) over device tensors
+    (include/orbx.h).  graph: covis_graph(...), updated in place.  counts (nkf,), kf_mp (nkf, cap), kf_rank (nkf,) or
+    None, pts (nmp, 12) int32 view of MAP_POINT_DTYPE, obs_ptr (nmp + 1,), obs (nobs, 2) as in local_map_device.
+    work: connections_work(...).  Returns status (ntargets,) int32: 0, CONN_EMPTY, CONN_NOSPC or CONN_INVALID."""
+    import torch
+    g, nkf, ccap = _graph_device("update_connections_device", graph)
+    if kf_mp.ndim != 2 or kf_mp.shape[0] != nkf:
+        raise ValueError("update_connections_device: kf_mp must be (nkf, cap)")
+    nt = int(targets.shape[0])
+    if status is None:
+        status = torch.zeros((max(nt, 1),), dtype=torch.int32, device=targets.device)[:nt]
+    elif tuple(status.shape) != (nt,) or status.dtype != torch.int32 or not status.is_contiguous():
+        raise ValueError("update_connections_device: status must be a contiguous int32 tensor of shape (%d,)" % nt)
+    _check("orbm_update_connections_device",
+           lib.orbm_update_connections_device(C.byref(g), nkf, ccap, _ptr(counts), _ptr(kf_mp), int(kf_mp.shape[1]),
+                                              _ptr(kf_rank), _ptr(pts), _ptr(obs_ptr), _ptr(obs),
+                                              int(obs_ptr.shape[0]) - 1, _ptr(targets), nt, int(th), int(root),
+                                              _ptr(status), _ptr(work), _work_bytes(work), _stream(stream)))
+    return status
+
+
+def erase_connections_device(graph, targets, work, kf_rank=None, status=None, stream=None):
+    """The connection part of KeyFrame::SetBadFlag for targets in sequence (include/orbx.h); graph is updated in
+    place.  Returns status (ntargets,) int32: 0 or CONN_INVALID."""
+    import torch
+    g, nkf, ccap = _graph_device("erase_connections_device", graph)
+    nt = int(targets.shape[0])
+    if status is None:
+        status = torch.zeros((max(nt, 1),), dtype=torch.int32, device=targets.device)[:nt]
+    elif tuple(status.shape) != (nt,) or status.dtype != torch.int32 or not status.is_contiguous():
+        raise ValueError("erase_connections_device: status must be a contiguous int32 tensor of shape (%d,)" % nt)
+    _check("orbm_erase_connections_device",
+           lib.orbm_erase_connections_device(C.byref(g), nkf, ccap, _ptr(kf_rank), _ptr(targets), nt, _ptr(status),
+                                             _ptr(work), _work_bytes(work), _stream(stream)))
+    return status
+
+
+def _getter_out(fn, out, shape, dt, device):
+    import torch
+    if out is None:
+        return torch.zeros(shape, dtype=dt, device=device)
+    if tuple(out.shape) != shape or out.dtype != dt or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous %s tensor of shape %s" % (fn, dt, shape))
+    return out
+
+
+def best_covisibles_device(graph, N, out=None, stream=None):
+    """GetBestCovisibilityKeyFrames(N) of every slot, (nkf, N) int32 padded with -1: with N = 10 the covis of
+    local_map_device and of the KeyFrameDatabase's device detection."""
+    import torch
+    g, nkf, ccap = _graph_device("best_covisibles_device", graph)
+    out = _getter_out("best_covisibles_device", out, (nkf, int(N)), torch.int32, graph["nord"].device)
+    _check("orbm_best_covisibles_device",
+           lib.orbm_best_covisibles_device(C.byref(g), nkf, ccap, int(N), _ptr(out), _stream(stream)))
+    return out
+
+
+def connected_mask_device(graph, t, out=None, stream=None):
+    """The membership of GetConnectedKeyFrames() of slot t, (nkf,) uint8: the connected of detect_loop_device."""
+    import torch
+    g, nkf, ccap = _graph_device("connected_mask_device", graph)
+    out = _getter_out("connected_mask_device", out, (nkf,), torch.uint8, graph["nconn"].device)
+    _check("orbm_connected_mask_device",
+           lib.orbm_connected_mask_device(C.byref(g), nkf, ccap, int(t), _ptr(out), _stream(stream)))
+    return out
+
+
+def covisibles_by_weight_device(graph, w, out=None, stream=None):
+    """The length GetCovisiblesByWeight(w) returns for every slot, (nkf,) int32 (0 when every weight is >= w, as in
+    the reference); the KeyFrames are graph["ord_kf"][f, :n]."""
+    import torch
+    g, nkf, ccap = _graph_device("covisibles_by_weight_device", graph)
+    out = _getter_out("covisibles_by_weight_device", out, (nkf,), torch.int32, graph["nord"].device)
+    _check("orbm_covisibles_by_weight_device",
+           lib.orbm_covisibles_by_weight_device(C.byref(g), nkf, ccap, int(w), _ptr(out), _stream(stream)))
+    return out
+
+
+def children_work_bytes(nkf):
+    """orbm_children_work_bytes: the scratch of one children_device call (0 for sizes the call refuses)."""
+    return int(lib.orbm_children_work_bytes(int(nkf)))
+
+
+def children_work(nkf, device):
+    """A zeroed scratch tensor for children_device; every call leaves it zeroed."""
+    import torch
+    nbytes = children_work_bytes(nkf)
+    if nbytes == 0:
+        raise ValueError("children_work: sizes out of range")
+    return torch.zeros(((nbytes + 3) // 4,), dtype=torch.int32, device=device)
+
+
+def children_device(parent, kf_bad, work, kf_rank=None, out=None, stream=None):
+    """GetChilds() of every slot as the CSR local_map_device reads.  parent (nkf,) int32, kf_bad (nkf,) uint8,
+    kf_rank (nkf,) int32 or None.  out: optional dict of child_ptr (nkf + 1,), child (nkf,) and status (1,) int32.
+    Returns that dict; status[0] is 0 or CONN_INVALID (then child_ptr and child are untouched)."""
+    import torch
+    nkf = int(parent.shape[0])
+    out = dict(out or {})
+    for k, n in (("child_ptr", nkf + 1), ("child", max(nkf, 1)), ("status", 1)):
+        out[k] = _getter_out("children_device", out.get(k), (n,), torch.int32, parent.device)
+    _check("orbm_children_device",
+           lib.orbm_children_device(_ptr(parent), _ptr(kf_bad), _ptr(kf_rank), nkf, _ptr(out["child_ptr"]),
+                                    _ptr(out["child"]), _ptr(out["status"]), _ptr(work), _work_bytes(work),
+                                    _stream(stream)))
+    return out
+
+
+def update_connections(graph, counts, kf_mp, pts, obs_ptr, obs, targets, th=15, root=-1, kf_rank=None, status=None,
+                       device=0):
+    """The same as update_connections_device on host arrays; synchronous.  graph: a dict of contiguous numpy arrays
+    as covis_graph(nkf, ccap) makes them, updated in place.  status: optional (ntargets,) int32 whose contents stand
+    where the call writes nothing.  Returns status."""
+    nkf, ccap = _graph_dims("update_connections", graph)
+    for k in _GRAPH_FIELDS:
+        dt = np.uint8 if k == "first" else np.int32
+        if not isinstance(graph[k], np.ndarray) or graph[k].dtype != dt or not graph[k].flags.c_contiguous:
+            raise ValueError("update_connections: graph[%r] must be a contiguous %s array" % (k, np.dtype(dt)))
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)
+    cn, km = i32(counts), i32(kf_mp)
+    p = np.ascontiguousarray(pts, MAP_POINT_DTYPE).reshape(-1)
+    op, ob = i32(obs_ptr), np.ascontiguousarray(obs, OBSERVATION_DTYPE).reshape(-1)
+    nmp = len(op) - 1
+    tg = i32(targets).reshape(-1)
+    rk = None if kf_rank is None else i32(kf_rank)
+    if not (km.ndim == 2 and km.shape[0] == nkf and len(cn) == nkf and len(p) == nmp and
+            (rk is None or len(rk) == nkf)):
+        raise ValueError("update_connections: array sizes disagree")
+    st = np.zeros(len(tg), np.int32) if status is None else status
+    if st.dtype != np.int32 or st.shape != (len(tg),) or not st.flags.c_contiguous:
+        raise ValueError("update_connections: status must be a contiguous int32 array of shape (%d,)" % len(tg))
+    g = CovisGraph(*[graph[k].ctypes.data for k in _GRAPH_FIELDS])
+    ip = lambda a: None if a is None or a.size == 0 else _i32p(a)
+    _check("orbm_update_connections",
+           lib.orbm_update_connections(device, C.byref(g), nkf, ccap, ip(cn), ip(km), int(km.shape[1]), ip(rk),
+                                       p.ctypes.data if nmp else None, _i32p(op), ob.ctypes.data if ob.size else None,
+                                       nmp, ip(tg), len(tg), int(th), int(root), ip(st)))
+    return st
 
 
 TIE_FIRST, TIE_LAST = 0, 1
