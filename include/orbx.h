@@ -906,6 +906,135 @@ orbx_status orbm_children_device(const int* d_parent, const uint8_t* d_kf_bad, c
                                  int* d_child_ptr, int* d_child, int* d_status, void* d_work, size_t work_bytes,
                                  void* stream);
 
+/* ---- LocalMapping's culls: MapPointCulling and KeyFrameCulling ----
+ * src/LocalMapping.cc:170-205 and :632-696 with the observation-side edits they cause: MapPoint::SetBadFlag
+ * (src/MapPoint.cc:151-168), MapPoint::EraseObservation (:111-137), MapPoint::GetFoundRatio (:236-240),
+ * KeyFrame::EraseMapPointMatch (src/KeyFrame.cc:222-227) and the tests and the observation loop of
+ * KeyFrame::SetBadFlag (:457-464, :469-471).  They run over the KeyFrame and MapPoint tables of
+ * orbm_local_map_device / orbm_update_connections_device, in place, so that the culls, the compaction, the erase of
+ * the culled KeyFrames' connections, the refresh and the next local map chain on one stream with no host copy.
+ *
+ * Tables: d_counts, d_kf_mp at stride cap (in and out), d_pts (flags in and out), d_obs_ptr / d_obs, d_ref as in
+ * orbm_refresh_map_points_device (in and out).  List order is the caller's std::map order; a list's live entries name
+ * distinct KeyFrames, as a std::map's keys do (not checked).  New columns: d_nobs[nmp] = the nObs counter of
+ * Observations(), a stereo observation counted twice (in and out); d_uright / d_depth = mvuRight / mvDepth at stride
+ * cap (d_uright NULL = monocular, all -1); d_kps = mvKeysUn at stride cap (only .octave is read); d_found, d_visible,
+ * d_first_kfid [nmp] = mnFound, mnVisible, mnFirstKFid; d_kf_noterase[nkf] = mbNotErase.
+ *
+ * Erased mask: d_obs_erased[d_obs_ptr[nmp]] bytes, in and out.  An entry whose byte is not 0 does not exist for any of
+ * these calls: whatever it holds has no effect and is not range-checked.  The calls never move an entry of d_obs, they
+ * set bytes, so the list order that decides the refresh's ties stands and the two culls run back to back;
+ * orbm_compact_observations_device then writes the CSR the other calls read.  Also not checked: a list's live entries
+ * name distinct KeyFrames, as a std::map's keys do; only a list that names a culled candidate twice makes an outcome
+ * depend on the order of execution.
+ *
+ * Range checks, each before the read it guards.  A list that does not ascend from >= 0 or is longer than
+ * ORBM_MAX_OBSERVATIONS, and a live observation whose kf is outside [0, nkf) or whose idx is outside
+ * [0, min(d_counts[kf], cap)), make the unit that walks the list -- a recent MapPoint, a candidate KeyFrame -- INVALID:
+ * its verdict is written and nothing else of it, and later units still run.  Every live entry of a walked list is
+ * checked, also where the reference leaves its loop early.  Limits: nkf <= ORBV_DB_MAX_KEYFRAMES, cap <=
+ * ORBM_MAX_FEATURES, 1 <= ccap <= ORBM_MAX_CONNECTIONS, nlevels in [1, 16], t in [0, nkf), root in [-1, nkf);
+ * ORBX_EINVAL otherwise, and for a NULL table.  All asynchronous on `stream`; nothing is allocated or read on the host.
+ *
+ * MapPointCulling over mlpRecentAddedMapPoints = d_recent[0 .. nrecent), MapPoint indices, each listed once;
+ * cur_kfid = mpCurrentKeyFrame->mnId, th_obs = 2 (monocular) or 3.  d_verdict[k], tested in the reference's order:
+ * ERASED_BAD flags bit 0 clear (:186); RATIO (float)found / (float)visible < 0.25f, the division correctly rounded, a
+ * NaN or +inf comparing false (:190); OBS (int)cur_kfid - (int)first_kfid >= 2 && nobs <= th_obs (:195); DROPPED_OLD
+ * that difference >= 3 (:200); KEPT; INVALID the index outside [0, nmp), or, for RATIO and OBS, a list check.  RATIO and
+ * OBS run SetBadFlag: flags bit 0 clears, every live observation (kf, idx) stores -1 at d_kf_mp[kf * cap + idx]
+ * whatever stands there (EraseMapPointMatch) and has its mask byte set; d_nobs keeps its value, as in the reference,
+ * and with it flags bit 1.  d_recent_out[0 .. *d_nrecent_out) = the KEPT points in list order (room for nrecent). */
+enum {
+    ORBM_CULL_KEPT = 0,
+    ORBM_CULL_ERASED_BAD = 1,
+    ORBM_CULL_RATIO = 2,
+    ORBM_CULL_OBS = 3,
+    ORBM_CULL_DROPPED_OLD = 4,
+    ORBM_CULL_INVALID = 5
+};
+
+orbx_status orbm_map_point_culling_device(const int* d_recent, int nrecent, int cur_kfid, int th_obs,
+                                          const int* d_counts, int* d_kf_mp, int nkf, int cap, orbm_map_point* d_pts,
+                                          const int* d_obs_ptr, const orbm_observation* d_obs, uint8_t* d_obs_erased,
+                                          int nmp, const int* d_nobs, const int* d_found, const int* d_visible,
+                                          const int* d_first_kfid, int* d_verdict, int* d_recent_out,
+                                          int* d_nrecent_out, void* stream);
+
+/* KeyFrameCulling of KeyFrame t.  The candidates are ord_kf[t][0 .. nord[t]) of `graph` (a host struct of device
+ * pointers; only ord_kf and nord are read) as they are when the call runs, GetVectorCovisibleKeyFrames(), and they are
+ * processed as if one after another: a candidate sees every edit of the ones before it.  Per candidate c:
+ *  1 c == root: SKIP_ROOT (:643); nothing is counted;
+ *  2 for every feature i < d_counts[c] with mp = d_kf_mp[c * cap + i] >= 0 and flags bit 0 set: with `stereo`
+ *    (!mbMonocular) a feature with depth > th_depth || depth < 0 is skipped (float compares: a NaN depth is counted);
+ *    otherwise nMPs++, and if d_nobs[mp] > 3 the live observations with kf != c and octave(kf, idx) <=
+ *    octave(c, i) + 1 are counted: three or more make the feature redundant (:651-691);
+ *  3 the KeyFrame is culled iff (double)nRed > 0.9 * (double)nMPs (:693);
+ *  4 a culled c with d_kf_noterase[c] set: TO_BE_ERASED and no edit (mbToBeErased, KeyFrame.cc:459-463);
+ *  5 CULLED otherwise: for every feature with mp >= 0, isBad() not asked (:470), the first live entry of mp's list
+ *    with kf == c, if any, is erased -- once per MapPoint, however many features of c name it: d_nobs[mp] -=
+ *    (d_uright[c * cap + that entry's idx] >= 0 ? 2 : 1); if d_ref[mp].kf == c, d_ref[mp] = the first remaining live
+ *    entry (left as it was when none remains); flags bit 1 = d_nobs[mp] > 0; if d_nobs[mp] <= 2, SetBadFlag as above
+ *    over the remaining entries.  d_kf_mp[c * cap + i] itself keeps naming the point.
+ * INVALID: c outside [0, nkf); d_counts[c] outside [0, cap]; a d_kf_mp[c] entry outside [-1, nmp); a list check of a
+ * list step 2 or step 5 walks; in step 2 an octave outside [0, nlevels), of feature i or of a counted observation.
+ * The checks of step 5 run before its first write.  nord[t] outside [0, ccap]: *d_ncand = -1, nothing is processed.
+ * Outputs: d_verdict[j] per candidate; d_nmps[j] and d_nred[j] for KEPT, CULLED and TO_BE_ERASED; d_culled[j] = c for
+ * CULLED and -1 otherwise, all ccap entries, which is the target list of orbm_erase_connections_device (a -1 target is
+ * ORBM_CONN_INVALID there and writes nothing); *d_nculled; *d_ncand = nord[t].  d_kf_bad, the connections, the
+ * spanning tree, mTcp and the Map / database erase stay with the caller; the verdict loop reads none of them.
+ * d_work: orbm_culling_work_bytes(nmp) bytes, 4-byte aligned, zeroed once by the caller and left zeroed by every
+ * call.  One workgroup walks the candidates: the cost grows with their number times a KeyFrame's features. */
+enum {
+    ORBM_KFCULL_KEPT = 0,
+    ORBM_KFCULL_SKIP_ROOT = 1,
+    ORBM_KFCULL_CULLED = 2,
+    ORBM_KFCULL_TO_BE_ERASED = 3,
+    ORBM_KFCULL_INVALID = 4
+};
+
+/* Pure host code, no device: the scratch size of one call; 0 for arguments the call itself refuses. */
+size_t orbm_culling_work_bytes(int nmp);
+
+orbx_status orbm_keyframe_culling_device(const orbm_covis_graph* graph, int nkf, int ccap, int t, int root,
+                                         const int* d_counts, int* d_kf_mp, int cap, const orbx_keypoint* d_kps,
+                                         const float* d_uright, const float* d_depth, float th_depth, int stereo,
+                                         int nlevels, const uint8_t* d_kf_noterase, orbm_map_point* d_pts,
+                                         const int* d_obs_ptr, const orbm_observation* d_obs, uint8_t* d_obs_erased,
+                                         orbm_observation* d_ref, int* d_nobs, int nmp, int* d_verdict, int* d_nmps,
+                                         int* d_nred, int* d_culled, int* d_nculled, int* d_ncand, void* d_work,
+                                         size_t work_bytes, void* stream);
+
+/* The stable compaction of (d_obs_ptr, d_obs, d_obs_erased): d_obs_ptr_out[nmp + 1] and d_obs_out (room for
+ * d_obs_ptr[nmp] entries) hold every live entry in list order -- the CSR the refresh, the local map and
+ * UpdateConnections read next.  Entries of d_obs_out past the new total keep their bits.  *d_status: 0, or
+ * ORBM_CONN_INVALID when a list does not ascend from >= 0 or is longer than ORBM_MAX_OBSERVATIONS; such a list is
+ * compacted as an empty one. */
+orbx_status orbm_compact_observations_device(const int* d_obs_ptr, const orbm_observation* d_obs,
+                                             const uint8_t* d_obs_erased, int nmp, int* d_obs_ptr_out,
+                                             orbm_observation* d_obs_out, int* d_status, void* stream);
+
+/* The same on host arrays, updated in place, on HIP device `device`; synchronous.  The argument checks run before any
+ * device call.  ORBX_EINVAL also when obs_ptr does not ascend from >= 0 or nkf < 1 (and, for the compaction, when a
+ * list is longer than ORBM_MAX_OBSERVATIONS).  What the device form leaves untouched keeps its bits here too.  `graph`
+ * holds host pointers, of which ord_kf and nord are read; verdict, nmps, nred and culled have ccap entries.  The
+ * scratch is the call's own. */
+orbx_status orbm_map_point_culling(int device, const int* recent, int nrecent, int cur_kfid, int th_obs,
+                                   const int* counts, int* kf_mp, int nkf, int cap, orbm_map_point* pts,
+                                   const int* obs_ptr, const orbm_observation* obs, uint8_t* obs_erased, int nmp,
+                                   const int* nobs, const int* found, const int* visible, const int* first_kfid,
+                                   int* verdict, int* recent_out, int* nrecent_out);
+
+orbx_status orbm_keyframe_culling(int device, const orbm_covis_graph* graph, int nkf, int ccap, int t, int root,
+                                  const int* counts, int* kf_mp, int cap, const orbx_keypoint* kps,
+                                  const float* uright, const float* depth, float th_depth, int stereo, int nlevels,
+                                  const uint8_t* kf_noterase, orbm_map_point* pts, const int* obs_ptr,
+                                  const orbm_observation* obs, uint8_t* obs_erased, orbm_observation* ref, int* nobs,
+                                  int nmp, int* verdict, int* nmps, int* nred, int* culled, int* nculled, int* ncand);
+
+orbx_status orbm_compact_observations(int device, const int* obs_ptr, const orbm_observation* obs,
+                                      const uint8_t* obs_erased, int nmp, int* obs_ptr_out,
+                                      orbm_observation* obs_out, int* status);
+
 /* ---- DBoW2 vocabulary (TemplatedVocabulary, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h) ----
  * Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:521-528, src/KeyFrame.cc:59-66) call
  * transform(descriptors, mBowVec, mFeatVec, 4); the FeatureVector it produces is the

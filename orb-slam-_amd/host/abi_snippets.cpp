@@ -267,6 +267,46 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
                             obs_ptr.data(), obs.data(), np, &new_kf, ntargets, 15, root, conn_status.data());
     if (conn_status[0] == ORBM_CONN_NOSPC || conn_status[0] == ORBM_CONN_INVALID) nlocal = 0;
 
+    // LocalMapping::Run: MapPointCulling ... KeyFrameCulling, then the compaction and the culled KeyFrames' connections
+    int *d_kf_mp_rw = nullptr, *d_recent = nullptr, *d_recent_out = nullptr, *d_nrecent_out = nullptr;
+    int *d_nobs = nullptr, *d_found = nullptr, *d_visible = nullptr, *d_first_kfid = nullptr, *d_mp_verdict = nullptr;
+    int *d_kf_verdict = nullptr, *d_nmps = nullptr, *d_nred = nullptr, *d_culled = nullptr, *d_nculled = nullptr;
+    int *d_ncull_cand = nullptr, *d_obs_ptr_out = nullptr, *d_compact_status = nullptr, *d_erase_status = nullptr;
+    uint8_t *d_obs_erased = nullptr, *d_kf_noterase = nullptr;
+    orbm_observation *d_ref_rw = nullptr, *d_obs_out = nullptr;
+    void* d_cull_work = nullptr;   // hipMalloc + hipMemset once
+    int nrecent = 500, cur_kfid = 321;
+    size_t cull_bytes = orbm_culling_work_bytes(nmp);
+    orbm_map_point_culling_device(d_recent, nrecent, cur_kfid, /*nThObs*/ 3, d_counts, d_kf_mp_rw, nkf, cap, d_mps_rw,
+                                  d_obs_ptr, d_obs, d_obs_erased, nmp, d_nobs, d_found, d_visible, d_first_kfid,
+                                  d_mp_verdict, d_recent_out, d_nrecent_out, stream);
+    orbm_keyframe_culling_device(&graph, nkf, ccap, new_kf, root, d_counts, d_kf_mp_rw, cap, d_kps_un, d_uright_t,
+                                 d_depth_t, /*mThDepth*/ 35.0f, /*!mbMonocular*/ 1, P.nlevels, d_kf_noterase, d_mps_rw,
+                                 d_obs_ptr, d_obs, d_obs_erased, d_ref_rw, d_nobs, nmp, d_kf_verdict, d_nmps, d_nred,
+                                 d_culled, d_nculled, d_ncull_cand, d_cull_work, cull_bytes, stream);
+    orbm_compact_observations_device(d_obs_ptr, d_obs, d_obs_erased, nmp, d_obs_ptr_out, d_obs_out, d_compact_status,
+                                     stream);
+    orbm_erase_connections_device(&graph, nkf, ccap, d_rank, d_culled, ccap, d_erase_status, d_conn_work, conn_bytes,
+                                  stream);
+    // ... and on host arrays
+    std::vector<int> recent(nrecent), recent_out(nrecent), mp_verdict(nrecent), nobs(np), found(np), visible(np);
+    std::vector<int> first_kfid(np), kf_verdict(ccap), nmps(ccap), nred(ccap), culled(ccap), obs_ptr_out(np + 1);
+    std::vector<uint8_t> obs_erased(obs.size()), kf_noterase(nkf);
+    std::vector<orbm_observation> cull_ref(np), obs_out(obs.size());
+    std::vector<float> kf_uright((size_t)nkf * cap, -1.0f), kf_depth((size_t)nkf * cap, -1.0f);
+    std::vector<orbx_keypoint> kf_kps((size_t)nkf * cap);
+    int nrecent_out = 0, nculled = 0, ncands = 0, compact_status = 0;
+    orbm_map_point_culling(0, recent.data(), nrecent, cur_kfid, 3, tcounts.data(), kf_mp.data(), nkf, cap, mps.data(),
+                           obs_ptr.data(), obs.data(), obs_erased.data(), np, nobs.data(), found.data(),
+                           visible.data(), first_kfid.data(), mp_verdict.data(), recent_out.data(), &nrecent_out);
+    orbm_keyframe_culling(0, &hgraph, nkf, ccap, new_kf, root, tcounts.data(), kf_mp.data(), cap, kf_kps.data(),
+                          kf_uright.data(), kf_depth.data(), 35.0f, 1, P.nlevels, kf_noterase.data(), mps.data(),
+                          obs_ptr.data(), obs.data(), obs_erased.data(), cull_ref.data(), nobs.data(), np, kf_verdict.data(),
+                          nmps.data(), nred.data(), culled.data(), &nculled, &ncands);
+    orbm_compact_observations(0, obs_ptr.data(), obs.data(), obs_erased.data(), np, obs_ptr_out.data(), obs_out.data(),
+                              &compact_status);
+    if (mp_verdict[0] == ORBM_CULL_INVALID || kf_verdict[0] == ORBM_KFCULL_INVALID) nlocal = 0;
+
     // ComputeBoW
     std::vector<int32_t> bw(n), node(n), ptr(n + 1), idx(n);
     std::vector<double> bv(n);

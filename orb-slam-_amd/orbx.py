@@ -53,6 +53,9 @@ EXPORTED = [
     "orbm_connections_work_bytes", "orbm_update_connections_device", "orbm_update_connections",
     "orbm_erase_connections_device", "orbm_best_covisibles_device", "orbm_connected_mask_device",
     "orbm_covisibles_by_weight_device", "orbm_children_work_bytes", "orbm_children_device",
+    "orbm_map_point_culling_device", "orbm_map_point_culling", "orbm_culling_work_bytes",
+    "orbm_keyframe_culling_device", "orbm_keyframe_culling", "orbm_compact_observations_device",
+    "orbm_compact_observations",
     "orbm_best2_csr_device", "orbm_best2_csr", "orbm_stereo_band", "orbm_stereo_band_device",
     "orbv_load_text", "orbv_create", "orbv_destroy", "orbv_info", "orbv_transform", "orbv_transform_batch_device",
     "orbv_score", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_batch_device", "orbv_db_erase",
@@ -302,6 +305,20 @@ def _load():
     L.orbm_children_work_bytes.argtypes = [C.c_int]
     L.orbm_children_work_bytes.restype = C.c_size_t
     L.orbm_children_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp]
+    L.orbm_map_point_culling_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp,
+                                                C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_map_point_culling.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp,
+                                         vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_culling_work_bytes.argtypes = [C.c_int]
+    L.orbm_culling_work_bytes.restype = C.c_size_t
+    L.orbm_keyframe_culling_device.argtypes = [P(CovisGraph), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp,
+                                               vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
+                                               C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.orbm_keyframe_culling.argtypes = [C.c_int, P(CovisGraph), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int,
+                                        vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int,
+                                        vp, vp, vp, vp, vp, vp]
+    L.orbm_compact_observations_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.orbm_compact_observations.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]
     L.orbm_best2_csr_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     L.orbm_best2_csr.argtypes = [C.c_int, u8p, C.c_int, u8p, C.c_int, i32p, i32p, C.c_int, i32p, i32p, i32p]
     L.orbm_stereo_band.argtypes = [C.c_int, vp, u8p, C.c_int, vp, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_float,
@@ -1109,6 +1126,207 @@ def update_connections(graph, counts, kf_mp, pts, obs_ptr, obs, targets, th=15, 
                                        p.ctypes.data if nmp else None, _i32p(op), ob.ctypes.data if ob.size else None,
                                        nmp, ip(tg), len(tg), int(th), int(root), ip(st)))
     return st
+
+
+# d_verdict values of orbm_map_point_culling_device and orbm_keyframe_culling_device (include/orbx.h)
+CULL_KEPT, CULL_ERASED_BAD, CULL_RATIO, CULL_OBS, CULL_DROPPED_OLD, CULL_INVALID = 0, 1, 2, 3, 4, 5
+KFCULL_KEPT, KFCULL_SKIP_ROOT, KFCULL_CULLED, KFCULL_TO_BE_ERASED, KFCULL_INVALID = 0, 1, 2, 3, 4
+
+
+def culling_work_bytes(nmp):
+    """orbm_culling_work_bytes: the scratch of one keyframe_culling_device call (0 for sizes the call refuses)."""
+    return int(lib.orbm_culling_work_bytes(int(nmp)))
+
+
+def culling_work(nmp, device):
+    """A zeroed scratch tensor for keyframe_culling_device; every call leaves it zeroed."""
+    import torch
+    nbytes = culling_work_bytes(nmp)
+    if nbytes == 0:
+        raise ValueError("culling_work: sizes out of range")
+    return torch.zeros(((nbytes + 3) // 4,), dtype=torch.int32, device=device)
+
+
+def _cull_out(fn, out, shapes, device):
+    import torch
+    out = dict(out or {})
+    for k, shape in shapes.items():
+        out[k] = _getter_out(fn, out.get(k), shape, torch.int32, device)
+    return out
+
+
+def map_point_culling_device(recent, cur_kfid, th_obs, counts, kf_mp, pts, obs_ptr, obs, obs_erased, nobs, found,
+                             visible, first_kfid, out=None, stream=None):
+    """LocalMapping::MapPointCulling over device tensors (include/orbx.h).  recent (nrecent,) int32 MapPoint indices;
+    counts (nkf,), kf_mp (nkf, cap), pts (nmp, 12) int32 view of MAP_POINT_DTYPE, obs_ptr (nmp + 1,), obs (nobs, 2) as
+    in local_map_device; obs_erased (nobs,) uint8; nobs, found, visible, first_kfid (nmp,) int32.  kf_mp, pts and
+    obs_erased are updated in place.  out: optional dict of verdict (nrecent,), recent_out (nrecent,) and nrecent_out
+    (1,) int32.  Returns that dict: verdict holds CULL_*, recent_out[:nrecent_out] the KEPT points in list order."""
+    if kf_mp.ndim != 2:
+        raise ValueError("map_point_culling_device: kf_mp must be (nkf, cap)")
+    nr = int(recent.shape[0])
+    out = _cull_out("map_point_culling_device", out, dict(verdict=(nr,), recent_out=(nr,), nrecent_out=(1,)),
+                    kf_mp.device)
+    _check("orbm_map_point_culling_device",
+           lib.orbm_map_point_culling_device(_ptr(recent), nr, int(cur_kfid), int(th_obs), _ptr(counts), _ptr(kf_mp),
+                                             int(kf_mp.shape[0]), int(kf_mp.shape[1]), _ptr(pts), _ptr(obs_ptr),
+                                             _ptr(obs), _ptr(obs_erased), int(obs_ptr.shape[0]) - 1, _ptr(nobs),
+                                             _ptr(found), _ptr(visible), _ptr(first_kfid), _ptr(out["verdict"]),
+                                             _ptr(out["recent_out"]), _ptr(out["nrecent_out"]), _stream(stream)))
+    return out
+
+
+def keyframe_culling_device(graph, t, counts, kf_mp, kps, depth, th_depth, stereo, nlevels, kf_noterase, pts, obs_ptr,
+                            obs, obs_erased, ref, nobs, work, root=-1, uright=None, out=None, stream=None):
+    """LocalMapping::KeyFrameCulling of KeyFrame t over device tensors (include/orbx.h): the candidates are
+    graph["ord_kf"][t, :graph["nord"][t]], processed as if one after another.  kps (nkf, cap, 7) int32 view of
+    KEYPOINT_DTYPE, uright / depth (nkf, cap) float32 (uright None = monocular; depth may be None unless stereo),
+    kf_noterase (nkf,) uint8, ref (nmp, 2) int32, the rest as in map_point_culling_device.  kf_mp, pts, obs_erased,
+    ref and nobs are updated in place.  work: culling_work(nmp, ...).  out: optional dict of verdict, nmps, nred,
+    culled (ccap,), nculled and ncand (1,) int32.  Returns that dict: verdict holds KFCULL_*, culled the targets of
+    erase_connections_device (-1 where a candidate was not culled)."""
+    g, nkf, ccap = _graph_device("keyframe_culling_device", graph)
+    if kf_mp.ndim != 2 or kf_mp.shape[0] != nkf:
+        raise ValueError("keyframe_culling_device: kf_mp must be (nkf, cap)")
+    out = _cull_out("keyframe_culling_device", out,
+                    dict(verdict=(ccap,), nmps=(ccap,), nred=(ccap,), culled=(ccap,), nculled=(1,), ncand=(1,)),
+                    kf_mp.device)
+    _check("orbm_keyframe_culling_device",
+           lib.orbm_keyframe_culling_device(C.byref(g), nkf, ccap, int(t), int(root), _ptr(counts), _ptr(kf_mp),
+                                            int(kf_mp.shape[1]), _ptr(kps), _ptr(uright), _ptr(depth),
+                                            float(th_depth), int(bool(stereo)), int(nlevels), _ptr(kf_noterase),
+                                            _ptr(pts), _ptr(obs_ptr), _ptr(obs), _ptr(obs_erased), _ptr(ref),
+                                            _ptr(nobs), int(obs_ptr.shape[0]) - 1, _ptr(out["verdict"]),
+                                            _ptr(out["nmps"]), _ptr(out["nred"]), _ptr(out["culled"]),
+                                            _ptr(out["nculled"]), _ptr(out["ncand"]), _ptr(work), _work_bytes(work),
+                                            _stream(stream)))
+    return out
+
+
+def compact_observations_device(obs_ptr, obs, obs_erased, out=None, stream=None):
+    """The stable compaction of the observation CSR under the erased mask (include/orbx.h).  out: optional dict of
+    obs_ptr (nmp + 1,), obs (nobs, 2) and status (1,) int32.  Returns that dict: the CSR the refresh, the local map
+    and update_connections_device read next; status[0] is 0 or CONN_INVALID."""
+    import torch
+    out = dict(out or {})
+    dev = obs_ptr.device
+    out["obs_ptr"] = _getter_out("compact_observations_device", out.get("obs_ptr"), tuple(obs_ptr.shape), torch.int32,
+                                 dev)
+    out["obs"] = _getter_out("compact_observations_device", out.get("obs"), tuple(obs.shape), torch.int32, dev)
+    out["status"] = _getter_out("compact_observations_device", out.get("status"), (1,), torch.int32, dev)
+    _check("orbm_compact_observations_device",
+           lib.orbm_compact_observations_device(_ptr(obs_ptr), _ptr(obs), _ptr(obs_erased), int(obs_ptr.shape[0]) - 1,
+                                                _ptr(out["obs_ptr"]), _ptr(out["obs"]), _ptr(out["status"]),
+                                                _stream(stream)))
+    return out
+
+
+def _inout(fn, name, a, dt, shape=None):
+    if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or \
+            (shape is not None and a.shape != shape):
+        raise ValueError("%s: %s must be a contiguous %s array%s" %
+                         (fn, name, np.dtype(dt), "" if shape is None else " of shape %s" % (shape,)))
+    return a
+
+
+def _vp(a):
+    return None if a is None or a.size == 0 else a.ctypes.data
+
+
+def map_point_culling(recent, cur_kfid, th_obs, counts, kf_mp, pts, obs_ptr, obs, obs_erased, nobs, found, visible,
+                      first_kfid, out=None, device=0):
+    """The same as map_point_culling_device on host arrays; synchronous.  kf_mp (nkf, cap) int32, pts MAP_POINT_DTYPE
+    and obs_erased uint8 must be contiguous numpy arrays and are updated in place.  out: optional dict of verdict and
+    recent_out (nrecent,) int32 whose contents stand where the call writes nothing.  Returns a dict of verdict,
+    recent_out and nrecent_out (an int)."""
+    fn = "map_point_culling"
+    i32 = lambda a: np.ascontiguousarray(a, np.int32).reshape(-1)
+    rc, cn, op = i32(recent), i32(counts), i32(obs_ptr)
+    nmp = len(op) - 1
+    km = _inout(fn, "kf_mp", kf_mp, np.int32)
+    p = _inout(fn, "pts", pts, MAP_POINT_DTYPE, (nmp,))
+    ob = np.ascontiguousarray(obs, OBSERVATION_DTYPE).reshape(-1)
+    er = _inout(fn, "obs_erased", obs_erased, np.uint8, (len(ob),))
+    no, fo, vi, fk = i32(nobs), i32(found), i32(visible), i32(first_kfid)
+    if not (km.ndim == 2 and len(cn) == km.shape[0] and len(no) == len(fo) == len(vi) == len(fk) == nmp):
+        raise ValueError("map_point_culling: array sizes disagree")
+    out = dict(out or {})
+    for k in ("verdict", "recent_out"):
+        out[k] = np.zeros(len(rc), np.int32) if out.get(k) is None else _inout(fn, k, out[k], np.int32, (len(rc),))
+    n = C.c_int(0)
+    _check("orbm_map_point_culling",
+           lib.orbm_map_point_culling(device, _vp(rc), len(rc), int(cur_kfid), int(th_obs), _vp(cn), _vp(km),
+                                      km.shape[0], km.shape[1], _vp(p), _vp(op), _vp(ob), _vp(er), nmp, _vp(no),
+                                      _vp(fo), _vp(vi), _vp(fk), _vp(out["verdict"]), _vp(out["recent_out"]),
+                                      C.addressof(n)))
+    out["nrecent_out"] = n.value
+    return out
+
+
+def keyframe_culling(graph, t, counts, kf_mp, kps, depth, th_depth, stereo, nlevels, kf_noterase, pts, obs_ptr, obs,
+                     obs_erased, ref, nobs, root=-1, uright=None, out=None, device=0):
+    """The same as keyframe_culling_device on host arrays; synchronous.  graph: a dict of numpy arrays as
+    covis_graph(nkf, ccap) makes them (ord_kf and nord are read).  kf_mp, pts, obs_erased, ref (OBSERVATION_DTYPE)
+    and nobs (int32) must be contiguous numpy arrays and are updated in place.  out: optional dict of verdict, nmps,
+    nred, culled (ccap,) int32 whose contents stand where the call writes nothing.  Returns a dict of those and of
+    nculled and ncand (ints)."""
+    fn = "keyframe_culling"
+    nkf, ccap = int(graph["ord_kf"].shape[0]), int(graph["ord_kf"].shape[1])
+    ok = _inout(fn, "graph['ord_kf']", graph["ord_kf"], np.int32)
+    on = _inout(fn, "graph['nord']", graph["nord"], np.int32, (nkf,))
+    i32 = lambda a: np.ascontiguousarray(a, np.int32).reshape(-1)
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    cn, op = i32(counts), i32(obs_ptr)
+    nmp = len(op) - 1
+    km = _inout(fn, "kf_mp", kf_mp, np.int32)
+    kp = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+    ur, de = f32(uright), f32(depth)
+    ne = np.ascontiguousarray(kf_noterase, np.uint8)
+    p = _inout(fn, "pts", pts, MAP_POINT_DTYPE, (nmp,))
+    ob = np.ascontiguousarray(obs, OBSERVATION_DTYPE).reshape(-1)
+    er = _inout(fn, "obs_erased", obs_erased, np.uint8, (len(ob),))
+    rf = _inout(fn, "ref", ref, OBSERVATION_DTYPE, (nmp,))
+    no = _inout(fn, "nobs", nobs, np.int32, (nmp,))
+    if not (km.ndim == 2 and km.shape[0] == nkf == len(cn) == len(ne) and kp.shape == km.shape and
+            (ur is None or ur.shape == km.shape) and (de is None or de.shape == km.shape)):
+        raise ValueError("keyframe_culling: array sizes disagree")
+    out = dict(out or {})
+    for k in ("verdict", "nmps", "nred", "culled"):
+        out[k] = np.zeros(ccap, np.int32) if out.get(k) is None else _inout(fn, k, out[k], np.int32, (ccap,))
+    g = CovisGraph()
+    g.ord_kf, g.nord = ok.ctypes.data, on.ctypes.data
+    ncul, ncand = C.c_int(0), C.c_int(0)
+    _check("orbm_keyframe_culling",
+           lib.orbm_keyframe_culling(device, C.byref(g), nkf, ccap, int(t), int(root), _vp(cn), _vp(km), km.shape[1],
+                                     _vp(kp), _vp(ur), _vp(de), float(th_depth), int(bool(stereo)), int(nlevels),
+                                     _vp(ne), _vp(p), _vp(op), _vp(ob), _vp(er), _vp(rf), _vp(no), nmp,
+                                     _vp(out["verdict"]), _vp(out["nmps"]), _vp(out["nred"]), _vp(out["culled"]),
+                                     C.addressof(ncul), C.addressof(ncand)))
+    out["nculled"], out["ncand"] = ncul.value, ncand.value
+    return out
+
+
+def compact_observations(obs_ptr, obs, obs_erased, out=None, device=0):
+    """The same as compact_observations_device on host arrays; synchronous.  out: optional dict of obs_ptr (nmp + 1,)
+    int32 and obs (nobs,) OBSERVATION_DTYPE whose contents stand where the call writes nothing.  Returns a dict of
+    obs_ptr, obs and status (an int)."""
+    fn = "compact_observations"
+    op = np.ascontiguousarray(obs_ptr, np.int32).reshape(-1)
+    ob = np.ascontiguousarray(obs, OBSERVATION_DTYPE).reshape(-1)
+    er = np.ascontiguousarray(obs_erased, np.uint8).reshape(-1)
+    if len(er) != len(ob):
+        raise ValueError("compact_observations: array sizes disagree")
+    out = dict(out or {})
+    out["obs_ptr"] = (np.zeros(len(op), np.int32) if out.get("obs_ptr") is None
+                      else _inout(fn, "obs_ptr", out["obs_ptr"], np.int32, (len(op),)))
+    out["obs"] = (np.zeros(len(ob), OBSERVATION_DTYPE) if out.get("obs") is None
+                  else _inout(fn, "obs", out["obs"], OBSERVATION_DTYPE, (len(ob),)))
+    st = C.c_int(0)
+    _check("orbm_compact_observations",
+           lib.orbm_compact_observations(device, _vp(op), _vp(ob), _vp(er), len(op) - 1, _vp(out["obs_ptr"]),
+                                         _vp(out["obs"]), C.addressof(st)))
+    out["status"] = st.value
+    return out
 
 
 TIE_FIRST, TIE_LAST = 0, 1
