@@ -572,6 +572,72 @@ orbx_status orbm_frustum(int device, const orbm_map_point* pts, int np, const fl
                          const orbm_pose_params* params, float viewing_cos_limit, orbm_proj_point* out,
                          int* ninview);
 
+/* ---- Optimizer::PoseOptimization(Frame*) ----
+ * src/Optimizer.cc:239-451: the motion-only bundle adjustment Tracking runs after every search (TrackReferenceKeyFrame
+ * src/Tracking.cc:827, TrackWithMotionModel :950, TrackLocalMap :992, Relocalization :1492-1523), with the g2o pieces
+ * it instantiates (Levenberg, BlockSolver_6_3, LinearSolverDense, the two OnlyPose edges, Huber, SE3Quat) restated on
+ * the device; its arithmetic order is fixed in DESIGN.md §3.  One workgroup per frame.
+ *
+ * Inputs, as the searches leave them: d_kps (mvKeysUn; x, y and octave are read), d_uright (mvuRight: < 0 makes the
+ * edge monocular, else stereo) and d_frame_mp (mvpMapPoints as indices into d_pts, -1 none) at f * fcap,
+ * d_fcounts[f] features; of an orbm_map_point x, y, z and flags bit 1 (Observations() > 0); of params fx, fy, cx,
+ * cy, bf, nlevels and inv_sigma2[]; d_pose_in[f * pose_stride] = row-major 3x4 mTcw, pose_stride 12 or 24 (the
+ * d_pose of orbm_project_search_device).
+ * Outputs: d_pose_out[f * 12] the optimised mTcw (the input pose where fewer than 3 features have a MapPoint; it
+ * may alias no input); d_outlier[f * fcap + i] = mvbOutlier[i], written for the features with a MapPoint only;
+ * d_ninliers[f] the return value (nInitialCorrespondences - nBad, 0 below 3 correspondences); d_trace[f] (may be
+ * NULL) per round the outer iterations run, the rejected Levenberg trials and nBad, the rounds run and
+ * nInitialCorrespondences; d_status[f] 0 or ORBM_POSE_OPT_INVALID.
+ * With ORBM_POSE_OPT_DISCARD the call also runs the loop that follows the optimiser in TrackReferenceKeyFrame and
+ * TrackWithMotionModel (src/Tracking.cc:830-848, :953-972): an outlier's d_frame_mp[i] becomes -1, its MapPoint index
+ * goes to d_frame_outlier[f * fcap + i] (else -1; the array orbm_local_map_device takes), its flag is cleared, and
+ * d_nmatches_map[f] counts the remaining features whose MapPoint has Observations() > 0.  Without the flag
+ * d_frame_mp is only read, d_frame_outlier may be NULL and d_nmatches_map[f] counts the same set among the
+ * non-outliers (mnMatchesInliers of TrackLocalMap, :1002-1020, outside localisation mode).  IncreaseFound,
+ * mbTrackInView and mnLastFrameSeen stay with the caller.
+ * Invalid: a count outside [0, fcap], a d_frame_mp entry outside [-1, nmp), an octave of a feature with a MapPoint
+ * outside [0, nlevels).  Of an invalid frame only d_status[f] is written.  Entries at and past d_fcounts[f] are not
+ * written.  fcap <= ORBM_MAX_FEATURES.  ORBX_EINVAL for a null or misaligned argument, an unknown flag and a
+ * pose_stride other than 12 or 24.  Allocates nothing; asynchronous on `stream`. */
+enum { ORBM_POSE_OPT_DISCARD = 1 };   /* flags */
+enum { ORBM_POSE_OPT_INVALID = 1 };   /* d_status bits */
+
+typedef struct {
+    int32_t iters[4];      /* SparseOptimizer::optimize's iterations of each round */
+    int32_t rejected[4];   /* Levenberg trials rejected and popped */
+    int32_t nbad[4];       /* nBad after the round's classification */
+    int32_t rounds;        /* rounds run: 0 (fewer than 3 correspondences), 1 (fewer than 10 edges) or 4 */
+    int32_t ncorr;         /* nInitialCorrespondences */
+} orbm_pose_opt_trace;
+
+orbx_status orbm_pose_optimization_device(const orbx_keypoint* d_kps, const float* d_uright, const int* d_fcounts,
+                                          int nframes, int fcap, int* d_frame_mp, const orbm_map_point* d_pts,
+                                          int nmp, const float* d_pose_in, int pose_stride,
+                                          const orbm_pose_params* params, int flags, float* d_pose_out,
+                                          uint8_t* d_outlier, int* d_frame_outlier, int* d_ninliers,
+                                          int* d_nmatches_map, orbm_pose_opt_trace* d_trace, int* d_status,
+                                          void* stream);
+
+/* Host path for one frame (host arrays: n features, nmp MapPoints, pose_in and pose_out 12 floats; frame_mp, outlier
+ * and frame_outlier are updated in place as above), on HIP device `device`.  Synchronous. */
+orbx_status orbm_pose_optimization(int device, const orbx_keypoint* kps, const float* uright, int n, int* frame_mp,
+                                   const orbm_map_point* pts, int nmp, const float* pose_in,
+                                   const orbm_pose_params* params, int flags, float* pose_out, uint8_t* outlier,
+                                   int* frame_outlier, int* ninliers, int* nmatches_map, orbm_pose_opt_trace* trace,
+                                   int* status);
+
+/* Test hooks, not part of the interface a caller builds on (they may change or go without notice).
+ * orbm_pose_optimization_host: the kernel's own code compiled for the CPU and run by one lane, the same arguments and
+ * results without a device; tests/test_pose_optimization.py compares it with its restatement bit for bit. */
+orbx_status orbm_pose_optimization_host(const orbx_keypoint* kps, const float* uright, int n, int* frame_mp,
+                                        const orbm_map_point* pts, int nmp, const float* pose_in,
+                                        const orbm_pose_params* params, int flags, float* pose_out, uint8_t* outlier,
+                                        int* frame_outlier, int* ninliers, int* nmatches_map,
+                                        orbm_pose_opt_trace* trace, int* status);
+
+/* Test hook: sin, cos and the cube of theta as the pose optimiser's SE3 exponential evaluates them (out3[0..2]). */
+void orbx_po_sincos_theta3(double theta, double* out3);
+
 /* ---- MapPoint refresh: ComputeDistinctiveDescriptors and UpdateNormalAndDepth ----
  * src/MapPoint.cc:242-307 and :330-371, which the reference runs for every MapPoint of the KeyFrame concerned
  * after a KeyFrame insertion, a Fuse and a bundle adjustment (src/LocalMapping.cc:152-153, 442-444, 526-527,

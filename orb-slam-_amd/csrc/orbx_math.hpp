@@ -117,6 +117,41 @@ ORBX_HD float fast_atan2_deg(float y, float x)
     return a;
 }
 
+// sin(th), cos(th) and th^3 for the pose optimiser's SE3 exponential (th = |omega| >= 0; DESIGN.md §3 "Pose
+// optimisation arithmetic").  A fixed sequence of double + - * that the host and the gfx950 code evaluate alike -- the
+// device math library and glibc differ by an ulp, and that ulp reaches the pose.  Reduction by quadrant with a
+// three-part pi/2 (k * kPO_p1 and k * kPO_p2 are exact for k < 2^20), then the published fdlibm minimax polynomials
+// on [-pi/4, pi/4] without their tail corrections.  Not correctly rounded: within 1 ulp of glibc on [1e-5, 4].
+constexpr double kPO_invpio2 = 6.36619772367581382433e-01;
+constexpr double kPO_p1 = 1.57079632673412561417e+00, kPO_p2 = 6.07710050630396597660e-11,
+                 kPO_p3 = 2.02226624871116645580e-21;
+constexpr double kPO_S1 = -1.66666666666666324348e-01, kPO_S2 = 8.33333333332248946124e-03,
+                 kPO_S3 = -1.98412698298579493134e-04, kPO_S4 = 2.75573137070700676789e-06,
+                 kPO_S5 = -2.50507602534068634195e-08, kPO_S6 = 1.58969099521155010221e-10;
+constexpr double kPO_C1 = 4.16666666666666019037e-02, kPO_C2 = -1.38888888888741095749e-03,
+                 kPO_C3 = 2.48015872894767294178e-05, kPO_C4 = -2.75573143513906633035e-07,
+                 kPO_C5 = 2.08757232129817482790e-09, kPO_C6 = -1.13596475577881948265e-11;
+
+ORBX_HD void po_sincos_theta3(double th, double* sinv, double* cosv, double* th3)
+{
+    *th3 = th * th * th;
+    const double kf = th * kPO_invpio2 + 0.5;
+    const long long k = kf < 9.0e15 ? (long long)kf : 0;   // a NaN fails the comparison: 0
+    const double kd = (double)k;
+    const double r = ((th - kd * kPO_p1) - kd * kPO_p2) - kd * kPO_p3;
+    const double z = r * r;
+    const double sp =
+        r + (z * r) * (kPO_S1 + z * (kPO_S2 + z * (kPO_S3 + z * (kPO_S4 + z * (kPO_S5 + z * kPO_S6)))));
+    const double cr = z * (kPO_C1 + z * (kPO_C2 + z * (kPO_C3 + z * (kPO_C4 + z * (kPO_C5 + z * kPO_C6)))));
+    const double cp = 1.0 - (0.5 * z - z * cr);
+    switch ((int)(k & 3)) {
+    case 0: *sinv = sp; *cosv = cp; break;
+    case 1: *sinv = cp; *cosv = -sp; break;
+    case 2: *sinv = -sp; *cosv = -cp; break;
+    default: *sinv = -cp; *cosv = sp; break;
+    }
+}
+
 // (float)(CV_PI/180.f), src/ORBextractor.cc:131
 constexpr float kFactorPI = (float)(3.1415926535897932384626433832795 / 180.f);
 

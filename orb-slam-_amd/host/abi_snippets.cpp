@@ -226,6 +226,42 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     orbm_frustum_batch_device(d_local_pts, d_nlocal, nframes, pcap, d_Tcw, &P, 0.5f, d_pts, d_ntomatch, stream);
     orbm_search_by_projection_device(d_kps_un, d_desc, d_uright, d_local_claimed, d_fcounts, nframes, cap, d_pts,
                                      d_local_pdesc, d_nlocal, pcap, &prm, d_match, d_nmatches, stream);
+    // Tracking::Track with the pose on the device: Optimizer::PoseOptimization in its three places.  d_Tcw_rw holds
+    // the frame's mTcw and is handed to the next frustum test / search as it is; d_outl is mvbOutlier.
+    float* d_Tcw_rw = nullptr;
+    float* d_Tcw_opt = nullptr;   // the optimised pose: may not alias the input
+    uint8_t* d_outl = nullptr;
+    int *d_frame_outlier_rw = nullptr, *d_ninliers = nullptr, *d_nmatches_map = nullptr, *d_po_status = nullptr;
+    orbm_pose_opt_trace* d_po_trace = nullptr;   // or NULL
+    // TrackReferenceKeyFrame (:827) / TrackWithMotionModel (:950): after SearchByBoW / SearchByProjection wrote
+    // d_frame_mp; the discard loop (:830-848, :953-972) runs inside the call
+    orbm_pose_optimization_device(d_kps_un, d_uright, d_fcounts, nframes, cap, d_frame_mp, d_mps_rw, nmp, d_Tcw_rw, 12,
+                                  &P, ORBM_POSE_OPT_DISCARD, d_Tcw_opt, d_outl, d_frame_outlier_rw, d_ninliers,
+                                  d_nmatches_map, d_po_trace, d_po_status, stream);
+    // TrackLocalMap: UpdateLocalMap takes the discarded outliers, the frustum test and the search the new pose ...
+    orbm_local_map_device(d_counts, d_kf_mp, d_kf_bad, d_rank, d_covis, d_child_ptr, d_child, d_parent, nkf, cap,
+                          d_mps_rw, d_pdesc_rw, d_obs_ptr, d_obs, nmp, d_fcounts, d_frame_mp, d_frame_outlier_rw,
+                          nframes, cap, d_local_kf, d_nlocal_kf, kfcap, d_ref_kf, d_local_mp, d_nlocal, d_local_pts,
+                          d_local_pdesc, pcap, d_local_claimed, d_lm_status, d_work, work_bytes, stream);
+    orbm_frustum_batch_device(d_local_pts, d_nlocal, nframes, pcap, d_Tcw_opt, &P, 0.5f, d_pts, d_ntomatch, stream);
+    orbm_search_by_projection_device(d_kps_un, d_desc, d_uright, d_local_claimed, d_fcounts, nframes, cap, d_pts,
+                                     d_local_pdesc, d_nlocal, pcap, &prm, d_match, d_nmatches, stream);
+    // ... and the third optimisation (:992): no discard, d_nmatches_map = mnMatchesInliers
+    orbm_pose_optimization_device(d_kps_un, d_uright, d_fcounts, nframes, cap, d_frame_mp, d_mps_rw, nmp, d_Tcw_opt, 12,
+                                  &P, 0, d_Tcw_rw, d_outl, nullptr, d_ninliers, d_nmatches_map, nullptr, d_po_status,
+                                  stream);
+    // Relocalization (:1492-1523): one candidate on host arrays, up to three times around the projection searches
+    {
+        std::vector<int> fmp(n, -1), fout(n, -1);
+        std::vector<uint8_t> outl(n, 0);
+        float Tcw_in[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, Tcw_out[12];
+        int nGood = 0, nMap = 0, po_status = 0;
+        orbm_pose_opt_trace po_trace;
+        orbm_pose_optimization(0, (const orbx_keypoint*)kps.data(), uright.data(), n, fmp.data(), mps.data(), np, Tcw_in,
+                               &P, 0, Tcw_out,
+                               outl.data(), fout.data(), &nGood, &nMap, &po_trace, &po_status);
+        if (po_status & ORBM_POSE_OPT_INVALID) nGood = 0;
+    }
     // ... and one frame on host arrays
     std::vector<int> kf_mp((size_t)nkf * cap, -1), kf_covis((size_t)nkf * 10, -1), child_ptr(nkf + 1), child;
     std::vector<int> parent(nkf, -1), frame_mp(n, -1), local_kf(kfcap), local_mp(pcap);

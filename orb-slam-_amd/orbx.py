@@ -48,6 +48,8 @@ EXPORTED = [
     "orbm_search_by_sim3_device", "orbm_search_by_sim3",
     "orbx_undistort_points", "orbx_image_bounds", "orbx_undistort_batch_device", "orbx_rgbd_stereo_batch_device",
     "orbx_rgbd_stereo", "orbm_frustum_batch_device", "orbm_frustum",
+    "orbm_pose_optimization_device", "orbm_pose_optimization", "orbm_pose_optimization_host",
+    "orbx_po_sincos_theta3",
     "orbm_refresh_map_points_device", "orbm_refresh_map_points", "orbm_triangulate_device", "orbm_triangulate",
     "orbm_local_map_work_bytes", "orbm_local_map_device", "orbm_local_map",
     "orbm_connections_work_bytes", "orbm_update_connections_device", "orbm_update_connections",
@@ -275,6 +277,13 @@ def _load():
                                    f32p]
     L.orbm_frustum_batch_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, P(PoseParams), C.c_float, vp, vp, vp]
     L.orbm_frustum.argtypes = [C.c_int, vp, C.c_int, f32p, P(PoseParams), C.c_float, vp, i32p]
+    L.orbm_pose_optimization_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int,
+                                                P(PoseParams), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    for fn in (L.orbm_pose_optimization, L.orbm_pose_optimization_host):
+        fn.argtypes = ([C.c_int] if fn is L.orbm_pose_optimization else []) + [
+            vp, vp, C.c_int, vp, vp, C.c_int, vp, P(PoseParams), C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_po_sincos_theta3.argtypes = [C.c_double, C.POINTER(C.c_double)]
+    L.orbx_po_sincos_theta3.restype = None
     L.orbm_refresh_map_points_device.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int,
                                                  C.c_int, P(PoseParams), vp, vp, vp, vp]
     L.orbm_refresh_map_points.argtypes = [C.c_int, C.c_int, vp, u8p, i32p, C.c_int, C.c_int, f32p, u8p, i32p, vp, vp,
@@ -681,6 +690,92 @@ def frustum(pts, pose, params, viewing_cos_limit=0.5, device=0):
     _check("orbm_frustum", lib.orbm_frustum(device, pp.ctypes.data, len(pp), _f32p(ps), C.byref(prm),
                                             viewing_cos_limit, out.ctypes.data, C.byref(nv)))
     return out[:len(pp)].copy(), nv.value
+
+
+POSE_OPT_DISCARD = 1    # orbm_pose_optimization*: flags
+POSE_OPT_INVALID = 1    # status bits
+POSE_OPT_TRACE_DTYPE = np.dtype([("iters", "<i4", (4,)), ("rejected", "<i4", (4,)), ("nbad", "<i4", (4,)),
+                                 ("rounds", "<i4"), ("ncorr", "<i4")])
+
+
+def pose_optimization_device(kps, uright, counts, frame_mp, pts, pose, params, flags=0, pose_out=None, outlier=None,
+                             frame_outlier=None, ninliers=None, nmatches_map=None, trace=None, status=None,
+                             stream=None):
+    """Optimizer::PoseOptimization over a batch of Frames: kps (B, fcap, 7) int32 (mvKeysUn), uright (B, fcap)
+    float32, counts (B,), frame_mp (B, fcap) int32 (mvpMapPoints as rows of pts, -1 none), pts (nmp, 12) int32 view
+    of MAP_POINT_DTYPE, pose (B, 12) or (B, 24) float32 mTcw, params: PoseParams.  outlier (B, fcap) uint8 =
+    mvbOutlier, updated for the features with a MapPoint (default: a new zeroed tensor).  trace: (B, 14) int32 view
+    of POSE_OPT_TRACE_DTYPE, False for none (default: a new one).  With POSE_OPT_DISCARD frame_mp is updated and
+    frame_outlier (B, fcap) int32 written.  Returns (pose_out (B, 12), outlier, frame_outlier, ninliers,
+    nmatches_map, trace, status)."""
+    import torch
+    B, fcap = kps.shape[0], kps.shape[1]
+    dev = kps.device
+    if pose_out is None:
+        pose_out = torch.empty((B, 12), dtype=torch.float32, device=dev)
+    if outlier is None:
+        outlier = torch.zeros((B, fcap), dtype=torch.uint8, device=dev)
+    if frame_outlier is None and flags & POSE_OPT_DISCARD:
+        frame_outlier = torch.empty((B, fcap), dtype=torch.int32, device=dev)
+    if ninliers is None:
+        ninliers = torch.empty((B,), dtype=torch.int32, device=dev)
+    if nmatches_map is None:
+        nmatches_map = torch.empty((B,), dtype=torch.int32, device=dev)
+    if trace is None:
+        trace = torch.empty((B, 14), dtype=torch.int32, device=dev)
+    elif trace is False:
+        trace = None
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    prm = PoseParams.from_buffer_copy(params)
+    _check("orbm_pose_optimization_device",
+           lib.orbm_pose_optimization_device(_ptr(kps), _ptr(uright), _ptr(counts), B, fcap, _ptr(frame_mp), _ptr(pts),
+                                             pts.shape[0], _ptr(pose), pose.shape[-1], C.byref(prm), flags,
+                                             _ptr(pose_out), _ptr(outlier),
+                                             _ptr(frame_outlier) if frame_outlier is not None else None,
+                                             _ptr(ninliers), _ptr(nmatches_map),
+                                             _ptr(trace) if trace is not None else None, _ptr(status),
+                                             _stream(stream)))
+    return pose_out, outlier, frame_outlier, ninliers, nmatches_map, trace, status
+
+
+def pose_optimization(kps, uright, frame_mp, pts, pose, params, flags=0, outlier=None, device=0, on_host=False):
+    """Optimizer::PoseOptimization on host arrays (one frame): kps KEYPOINT_DTYPE (mvKeysUn), uright float32,
+    frame_mp int32, pts MAP_POINT_DTYPE, pose 3x4 mTcw, outlier uint8 = mvbOutlier on entry (default zeros).
+    on_host=True runs the kernel's code on the CPU (orbm_pose_optimization_host).  Returns a dict: pose (12,)
+    float32, outlier, frame_mp, frame_outlier, ninliers, nmatches_map, trace (POSE_OPT_TRACE_DTYPE scalar), status."""
+    k = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+    n = len(k)
+    ur = np.ascontiguousarray(uright, np.float32)
+    mp = np.array(frame_mp, np.int32).reshape(-1)
+    pp = np.ascontiguousarray(pts, MAP_POINT_DTYPE)
+    ps = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(-1)[:12])
+    ol = np.zeros(n, np.uint8) if outlier is None else np.array(outlier, np.uint8).reshape(-1)
+    assert len(ur) == n and len(mp) == n and len(ol) == n
+    pad = lambda a: a if n else np.zeros(1, a.dtype)   # noqa: E731
+    k, ur, mp, ol = pad(k), pad(ur), pad(mp), pad(ol)
+    fo = np.full(max(n, 1), -1, np.int32)
+    po = np.zeros(12, np.float32)
+    tr = np.zeros(1, POSE_OPT_TRACE_DTYPE)
+    ni, nm, st = C.c_int(0), C.c_int(0), C.c_int(0)
+    prm = PoseParams.from_buffer_copy(params)
+    args = (k.ctypes.data, ur.ctypes.data, n, mp.ctypes.data, pp.ctypes.data if len(pp) else None, len(pp),
+            ps.ctypes.data, C.byref(prm), flags, po.ctypes.data, ol.ctypes.data, fo.ctypes.data,
+            C.cast(C.byref(ni), C.c_void_p), C.cast(C.byref(nm), C.c_void_p), tr.ctypes.data,
+            C.cast(C.byref(st), C.c_void_p))
+    if on_host:
+        _check("orbm_pose_optimization_host", lib.orbm_pose_optimization_host(*args))
+    else:
+        _check("orbm_pose_optimization", lib.orbm_pose_optimization(device, *args))
+    return dict(pose=po, outlier=ol[:n], frame_mp=mp[:n], frame_outlier=fo[:n], ninliers=ni.value,
+                nmatches_map=nm.value, trace=tr[0], status=st.value)
+
+
+def po_sincos_theta3(theta):
+    """(sin, cos, theta ** 3) as the pose optimiser's SE3 exponential evaluates them (host code)."""
+    o = (C.c_double * 3)()
+    lib.orbx_po_sincos_theta3(float(theta), o)
+    return o[0], o[1], o[2]
 
 
 def refresh_map_points_device(what, kps, desc, counts, pose, kf_bad, obs_ptr, obs, ref, max_obs, params, pts, pdesc,
