@@ -169,6 +169,13 @@ orbx_status orbx_debug_fill_workspace(orbx_handle* h, int value);
  * hook: per-launch roofline figures): counts[0] pyramid, [1] FAST, [2] quadtree, [3] describe;
  * counts[4]: bit l set if a pyramid launch reads level l. */
 orbx_status orbx_debug_launches(orbx_handle* h, int rows, int cols, int batch, int* counts, int n);
+/* The quadtree form each level of one batched extract of `batch` frames of rows x cols runs (test hook;
+ * launches nothing).  plan[8 * l ..]: workgroup size, keypoints per thread, 1 if the node arrays live in
+ * global memory, 1 for the wide form (a side above 4096 px), node-list capacity, cell capacity, the bytes
+ * the gather has for its owner map (it takes that path while 4 * cells + 2 * candidates fit), and the
+ * index of the level's launch (levels of one launch share it).  `nlevels`: rows `plan` holds, at least
+ * the extractor's level count. */
+orbx_status orbx_debug_qt_plan(orbx_handle* h, int rows, int cols, int batch, int* plan, int nlevels);
 
 /* ---- Stereo (Frame::ComputeStereoMatches, src/Frame.cc:630-872) ----
  * bf = Camera.bf (mbf), fx = K(0,0).  The search limits follow :676-681 with

@@ -689,6 +689,19 @@ orbx_status orbx_debug_launches(orbx_handle* h, int rows, int cols, int batch, i
     return ORBX_OK;
 }
 
+orbx_status orbx_debug_qt_plan(orbx_handle* h, int rows, int cols, int batch, int* plan, int nlevels)
+{
+    if (!h || !plan || batch < 1) return ORBX_EINVAL;
+    DeviceGuard guard(h->device);
+    const orbx_status st = ensure_geometry(h, rows, cols);
+    if (st != ORBX_OK) return st;
+    const Geometry& g = h->geom;
+    if (nlevels < g.nlevels) return ORBX_EINVAL;
+    static_assert(sizeof(QtLevelPlan) == 8 * sizeof(int), "orbx_debug_qt_plan rows are eight ints");
+    qt_report(g, batch, (QtLevelPlan*)plan);
+    return ORBX_OK;
+}
+
 // Host-path copies between the pinned staging block and device memory as kernels on the extraction's own
 // queue: an SDMA copy (hipMemcpy*Async) costs its own ~11 us for a 640x480 image plus ~11 us before the
 // compute queue sees it has finished; a kernel reading or writing the mapped pinned block over PCIe needs

@@ -73,6 +73,12 @@ struct QtGroup {
 };
 constexpr int kQtMaxGroups = kMaxLevels + 1;
 int qt_plan(const Geometry& g, int batch, QtGroup* out);   // returns the group count
+// per level: the launched template (nt, kpt, glob, wide), its capacities, the gather's owner-map room in bytes
+// and the index of its launch (eight ints, the rows of orbx_debug_qt_plan)
+struct QtLevelPlan {
+    int nt, kpt, glob, wide, lcap, cellcap, gather_room, launch;
+};
+void qt_report(const Geometry& g, int batch, QtLevelPlan* out);   // out[g.nlevels]
 // host: decides qt_glob per level and lays out the per-frame global node block (qtg_*); false if a
 // level cannot be run at all
 bool qt_prepare(Geometry& g);

@@ -144,7 +144,7 @@ __device__ __forceinline__ uint32_t cell_slot_fix(uint32_t w, const uint32_t* sc
 }
 
 struct QtLayout {
-    size_t scan, rect, cnt, srank, npos, snode, sinfo, ccnt, cpos, vprev, vnew, skey, best, wsum, sh, kpa, total;
+    size_t scan, rect, cnt, srank, npos, snode, sinfo, ccnt, cpos, vprev, vnew, skey, best, wsum, sh, kpa, escan, total;
 };
 
 // Keypoints held in LDS instead of registers (kpa, one dword per register slot) by the wide LDS-node
@@ -183,6 +183,9 @@ __host__ __device__ inline QtLayout qt_layout(int lcap, int cellcap, int ixb = 2
     L.wsum = take(sizeof(uint32_t) * (QT_NW + 1));
     L.sh = take(sizeof(int) * 16);
     L.kpa = take(sizeof(uint32_t) * kpn);
+    // the global-node form's prefixes of expandable children (step C), which the LDS forms pack into the high
+    // halves of scan: no bytes with 16-bit indices
+    L.escan = take(ixb == 4 ? sizeof(uint32_t) * (lcap + 1) : 0);
     L.total = o;
     return L;
 }
@@ -193,6 +196,9 @@ constexpr size_t kQtGlobWsum = 0, kQtGlobSh = 64, kQtGlobSmem = 128;
 // The LDS form packs a keypoint's child slot (4 * lcap) beside its node index in one 32-bit word.
 constexpr size_t kQtLdsMax = 160 * 1024;
 constexpr int kQtLdsMaxList = 16383;
+// Step C of a round scans (children, expandable children) per split node in the 16-bit halves of one word: a
+// list of lcap nodes splits into at most 4 * lcap children.  The global-node form scans the two apart.
+static_assert(4 * kQtLdsMaxList < 0x10000, "the LDS forms' packed child / expandable-child prefixes would wrap");
 
 // shared scalar slots
 // SH_BIG: some phase-2 node holds more than 0xFFFF keys, so the packed (size, creation) sort key overflows
@@ -290,6 +296,7 @@ __device__ __forceinline__ void qt_nodes(const int l, const int f, const Geometr
     Ix* vprev = (Ix*)(nb + Ly.vprev);
     Ix* vnew = (Ix*)(nb + Ly.vnew);
     uint32_t* skey = (uint32_t*)(nb + Ly.skey);
+    uint32_t* escan = (uint32_t*)(nb + Ly.escan);   // kG only
     unsigned long long* best = (unsigned long long*)(nb + Ly.best);
     uint32_t* wsum = (uint32_t*)(smem + (kG ? kQtGlobWsum : Ly.wsum));
     int* sh = (int*)(smem + (kG ? kQtGlobSh : Ly.sh));
@@ -665,7 +672,8 @@ __device__ __forceinline__ void qt_nodes(const int l, const int f, const Geometr
         __syncthreads();
         QT_STAMP(9, qt_t);
 
-        // ---- C: children (low half) and expandable children (high half) per split rank ----
+        // ---- C: children (low half) and expandable children (high half) per split rank; kG scans the halves
+        // apart (scan, escan): its lists are not bounded by kQtLdsMaxList, and a packed prefix would wrap ----
         auto kids = [&](int s) -> uint32_t {
             const int p = snode[s];
             uint32_t v = 0;
@@ -676,25 +684,37 @@ __device__ __forceinline__ void qt_nodes(const int l, const int f, const Geometr
             }
             return v;
         };
-        const uint32_t T = block_scan_fn<QT_NT>(scan, S, wsum, kids);
+        uint32_t preC, preE;   // prefixes at kk: children, expandable children
+        if constexpr (kG) {
+            preC = block_scan_fn<QT_NT>(scan, S, wsum, [&](int s) { return kids(s) & 0xFFFFu; });
+            preE = block_scan_fn<QT_NT>(escan, S, wsum, [&](int s) { return kids(s) >> 16; });
+        } else {
+            const uint32_t T = block_scan_fn<QT_NT>(scan, S, wsum, kids);
+            preC = T & 0xFFFFu;
+            preE = T >> 16;
+        }
+        auto pre_c = [&](int s) -> uint32_t { return kG ? scan[s] : scan[s] & 0xFFFFu; };
+        auto pre_e = [&](int s) -> uint32_t { return kG ? escan[s] : scan[s] >> 16; };
         int kk = S;
-        uint32_t pre = T;   // prefix at kk
         if (phase == 2) {
             // how many candidates are actually split: the size after splitting j grows with j (a split
             // node leaves >= 1 child), so the one j that crosses N writes
             for (int j = tid; j < S; j += QT_NT) {
-                const int cs = (int)(kids(j) & 0xFFFFu), sj = (int)(scan[j] & 0xFFFFu);
+                const int cs = (int)(kids(j) & 0xFFFFu), sj = (int)pre_c(j);
                 if (L + sj + cs - (j + 1) >= N && L + sj - j < N) sh[SH_KK] = j + 1;
             }
             __syncthreads();
             kk = sh[SH_KK];
-            if (kk < S) pre = scan[kk];
+            if (kk < S) {
+                preC = pre_c(kk);
+                preE = pre_e(kk);
+            }
             block_scan_fn<QT_NT>(scan2, L, wsum, [&](int p) {
                 return (srank[p] != kNoneI && (int)srank[p] < kk) ? 1u : 0u;
             });
         }
         QT_STAMP(10, qt_t);
-        const int Ctot = (int)(pre & 0xFFFFu), nexp = (int)(pre >> 16);
+        const int Ctot = (int)preC, nexp = (int)preE;
         const int newL = Ctot + (L - kk);
         if (newL > lcap) {
             if (tid == 0) {
@@ -707,7 +727,6 @@ __device__ __forceinline__ void qt_nodes(const int l, const int f, const Geometr
         // ---- D ----
         for (int s = tid; s < kk; s += QT_NT) {
             const int p = snode[s];
-            const uint32_t ps = scan[s];
             uint32_t c4[4];
             int cs = 0;
 #pragma unroll
@@ -715,8 +734,8 @@ __device__ __forceinline__ void qt_nodes(const int l, const int f, const Geometr
                 c4[q] = ccnt[4 * p + q];
                 cs += c4[q] > 0;
             }
-            const int pos0 = Ctot - (int)(ps & 0xFFFFu) - cs;   // later splits are pushed in front
-            int e = (int)(ps >> 16);
+            const int pos0 = Ctot - (int)pre_c(s) - cs;   // later splits are pushed in front
+            int e = (int)pre_e(s);
             const uint32_t w = sinfo[p];
             const int mx = (int)kp_x(w, xb), my = (int)kp_y(w, xb);
             const int x0 = cx0[p], x1 = cx1[p], y0 = cy0[p], y1 = cy1[p];
@@ -900,6 +919,22 @@ int qt_plan(const Geometry& g, int batch, QtGroup* out)
         l0 = l1;
     }
     return n;
+}
+
+// What launch_quadtree runs for each level of a batch, read from the plan and the layout (orbx_debug_qt_plan).
+// gather_room: the bytes the gather compares 4 * ncells + 2 * n against when it picks the owner map (gregion).
+void qt_report(const Geometry& g, int batch, QtLevelPlan* out)
+{
+    QtGroup grp[kQtMaxGroups];
+    const int ng = qt_plan(g, batch, grp);
+    for (int i = 0; i < ng; ++i) {
+        const QtGroup& q = grp[i];
+        const int nt = q.glob ? kQtGlobNT : q.nt, kpt = q.glob ? kQtGlobKPT : q.kpt;
+        const QtLayout Ly = qt_layout(q.lcap, q.cellcap, q.glob ? 4 : 2, qt_kpn(nt, kpt, q.glob));
+        for (int l = q.l0; l < q.l0 + q.nl; ++l)
+            out[l] = QtLevelPlan{nt, kpt, q.glob, g.kp_xbits != 12, q.lcap, q.cellcap,
+                                 q.glob ? 0 : (int)(Ly.wsum - Ly.rect), i};
+    }
 }
 
 bool qt_prepare(Geometry& g)

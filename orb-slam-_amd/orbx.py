@@ -39,7 +39,7 @@ BLUR_SCALAR, BLUR_SSE2, BLUR_BITEXACT = 0, 1, 2
 EXPORTED = [
     "orbx_create", "orbx_destroy", "orbx_get_tables", "orbx_capacity", "orbx_set_cv_modes", "orbx_extract", "orbx_get_level",
     "orbx_extract_batch_device", "orbx_extract_stage_device", "orbx_sync", "orbx_set_timing", "orbx_get_stage_times",
-    "orbx_debug_pyramid", "orbx_debug_candidates", "orbx_debug_fill_workspace", "orbx_debug_launches", "orbm_descriptor_distance", "orbm_allpairs_device", "orbm_allpairs",
+    "orbx_debug_pyramid", "orbx_debug_candidates", "orbx_debug_fill_workspace", "orbx_debug_launches", "orbx_debug_qt_plan", "orbm_descriptor_distance", "orbm_allpairs_device", "orbm_allpairs",
     "orbm_search_init_batch_device", "orbm_search_for_initialization_device", "orbm_search_for_initialization",
     "orbx_compute_stereo_matches", "orbx_stereo_batch_device",
     "orbm_bow_search_device", "orbm_bow_search",
@@ -215,6 +215,7 @@ def _load():
     L.orbx_debug_candidates.argtypes = [vp, C.c_int, C.c_int, i32p, C.c_int, i32p]
     L.orbx_debug_fill_workspace.argtypes = [vp, C.c_int]
     L.orbx_debug_launches.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, C.c_int]
+    L.orbx_debug_qt_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, C.c_int]
     L.orbm_descriptor_distance.argtypes = [u8p, u8p]
     L.orbm_allpairs_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.orbm_allpairs.argtypes = [C.c_int, u8p, C.c_int, u8p, C.c_int, C.c_int, vp, vp, vp, vp]
@@ -538,6 +539,17 @@ class ORBextractor:
         _check("orbx_debug_launches", lib.orbx_debug_launches(self._h, rows, cols, batch,
                                                               c.ctypes.data_as(C.POINTER(C.c_int)), 5))
         return dict(zip(("pyramid", "fast", "quadtree", "describe", "pyramid_sources"), (int(v) for v in c)))
+
+    def debug_qt_plan(self, rows, cols, batch):
+        """The quadtree form of each level of one batched extract (orbx_debug_qt_plan), a dict per level: nt
+        (workgroup size), kpt (keypoints per thread), glob (node arrays in global memory), wide, lcap, cellcap,
+        gather_room (bytes: the owner map runs while 4 * cells + 2 * candidates fit) and launch (its index)."""
+        nl = self.params.nlevels
+        c = np.zeros((nl, 8), np.int32)
+        _check("orbx_debug_qt_plan", lib.orbx_debug_qt_plan(self._h, rows, cols, batch,
+                                                            c.ctypes.data_as(C.POINTER(C.c_int)), nl))
+        names = ("nt", "kpt", "glob", "wide", "lcap", "cellcap", "gather_room", "launch")
+        return [dict(zip(names, (int(v) for v in row))) for row in c]
 
 
 def compute_stereo_matches(left, right, kps_l, desc_l, kps_r, desc_r, bf, fx):
