@@ -695,6 +695,107 @@ orbx_status orbm_refresh_map_points(int device, int what, const orbx_keypoint* k
                                     int np, const orbm_pose_params* params, orbm_map_point* pts, uint8_t* pdesc,
                                     int* best);
 
+/* ---- Sim3Solver: the RANSAC of LoopClosing::ComputeSim3 between SearchByBoW and SearchBySim3 ----
+ * src/Sim3Solver.cc (constructor :37-112, SetRansacParameters :114-138, iterate :140-207, ComputeSim3 :226-337,
+ * CheckInliers :340-364, Project / FromCameraToImage :382-423), as src/LoopClosing.cc:274-323 drives it.  Horn's
+ * closed-form 3-point solve (cv::eigen's Jacobi on the 4x4 N, cv::Rodrigues) and the projection test of every
+ * hypothesis, batched over solvers and iterations.  The arithmetic order is fixed in DESIGN.md §3 "Sim3 solver
+ * arithmetic"; parity with a real OpenCV is unpinned.  OptimizeSim3 stays with the caller.
+ *
+ * orbm_sim3_setup_device = the constructor and SetRansacParameters, one solver per pair p: KF1 = d_pair_a[p]
+ * (mpCurrentKF), KF2 = d_pair_b[p].  KeyFrame table: the layout of orbm_search_by_sim3_device (d_kps = mvKeysUn,
+ * d_counts, cap, d_pose[f * 12] = row-major 3x4 Tcw) plus d_kf_mp[f * cap + i] = GetMapPointMatches()[i] as an index
+ * into d_pts, -1 none.  MapPoint table: d_pts (x, y, z and flags bit 0 = !isBad() are read), nmp, and the
+ * observation lists d_obs[d_obs_ptr[m] .. d_obs_ptr[m + 1]) with d_obs_erased (NULL = none erased) as in
+ * orbm_map_point_culling_device.  d_match12[p * match_stride + i1] = idx2 or -1 as orbm_bow_search_device
+ * (ORBM_BOW_KF_KF) leaves it, match_stride >= cap: vpMatched12[i1] = d_kf_mp[b * cap + idx2].  Both cameras share
+ * one orbm_pose_params; fx, fy, cx, cy, nlevels and scale[] are read (mvLevelSigma2[o] = scale[o] * scale[o]).
+ * A pair survives as the reference has it: both MapPoints present and not bad, and GetIndexInKeyFrame -- the idx
+ * of the point's live observation whose kf is the KeyFrame -- >= 0 on both sides; the keypoints are those at
+ * indexKF1 / indexKF2, not at i1 / idx2.  The stored error bounds are (float)(size_t)(9.210 * sigma2): mvnMaxError
+ * is a vector<size_t>.  The survivors are kept in i1 order in d_work.
+ * d_maxits[n], n <= cap, is mRansacMaxIts for N = n: orbm_sim3_ransac_iterations(n, probability, min_inliers,
+ * max_iterations), filled by the caller once per parameter set.  Outputs: d_n[p] = N, d_iterations[p] =
+ * d_best_inliers[p] = 0 (mnIterations, mnBestInliers), d_status[p] = 0 or ORBM_SIM3_INVALID.  Invalid: a KeyFrame
+ * slot outside [0, nkf), a count outside [0, cap], a d_match12 entry outside [-1, count of KF2), a d_kf_mp entry
+ * outside [-1, nmp), a descending d_obs_ptr, the observation of a survivor with idx outside its KeyFrame's count,
+ * or its keypoint's octave outside [0, nlevels).  Of an invalid solver only d_status[p] is written, and iterate
+ * gives it no result.
+ *
+ * orbm_sim3_iterate_device = iterate(nit, bNoMore, vbInliers, nInliers) of every solver.  Iterations k < nit are
+ * evaluated as independent hypotheses and the reference's sequential rule is then applied: with best_k =
+ * max(d_best_inliers, inliers of the iterations before k) the call returns at the first k whose inliers are >=
+ * best_k and > min_inliers; it stops when d_iterations + k + 1 reaches mRansacMaxIts.  Iteration k of solver p
+ * draws its three points from d_rand[d_rand_off[p] + 3k .. + 2], raw rand() values in [0, 2^31 - 1], through
+ * DUtils::Random::RandomInt and the swap-with-back removal of :163-177.  fix_scale = mbFixScale.
+ * Outputs per solver: d_sim3[p * 13] = s12, R12 (row-major), t12 of the returned hypothesis, all 0 without one
+ * (orbm_search_by_sim3_device: s12 not > 0 matches nothing); d_inliers12[p * cap + i1] = vbInliers (and the
+ * d_already1 of orbm_search_by_sim3_device); d_already2[p * cap + i2] = vbAlreadyMatched2 as SearchBySim3
+ * :1200-1210 derives it from the inliers, through GetIndexInKeyFrame(pKF2); d_ninliers[p] = nInliers; d_nomore[p]
+ * = bNoMore; d_used[p] = the iterations this call consumed (so the draws of the next call start 3 * d_used
+ * further).  d_iterations / d_best_inliers are read and updated.  N < min_inliers is bNoMore with nothing else
+ * done; a negative d_iterations (a state the calls never leave) is bNoMore without a result too.  nsolvers and nit
+ * are at most 65535 each (orbm_sim3_workspace_bytes returns 0 beyond).  nit in [1, max_iters_per_call of the
+ * workspace]; min_inliers >= 3 (the reference's sampling is undefined
+ * below it).  d_work of orbm_sim3_workspace_bytes(nsolvers, cap, max_iters_per_call) bytes, 16-byte aligned, keeps
+ * the solvers between the calls.  ORBX_EINVAL for a null or misaligned argument, cap outside [1,
+ * ORBM_MAX_FEATURES], nsolvers or nit above 65535, min_inliers < 3 or a workspace too small.  Both calls allocate nothing and are asynchronous
+ * on `stream`. */
+enum { ORBM_SIM3_INVALID = 1 };   /* d_status bits */
+
+size_t orbm_sim3_workspace_bytes(int nsolvers, int cap, int max_iters_per_call);
+
+/* mRansacMaxIts of SetRansacParameters for N = n (:125-135), the reference's expression on the host's libm: 1 when
+ * min_inliers == n, else max(1, min(ceil(log(1 - p) / log(1 - pow(eps, 3))), max_iterations)) with float eps =
+ * (float)min_inliers / n.  A quotient that is not a number or outside int converts as x86 does (INT_MIN). */
+int orbm_sim3_ransac_iterations(int n, double probability, int min_inliers, int max_iterations);
+
+orbx_status orbm_sim3_setup_device(const orbx_keypoint* d_kps, const int* d_counts, int nkf, int cap,
+                                   const float* d_pose, const int* d_kf_mp, const orbm_map_point* d_pts, int nmp,
+                                   const int* d_obs_ptr, const orbm_observation* d_obs, const uint8_t* d_obs_erased,
+                                   const int* d_pair_a, const int* d_pair_b, int nsolvers, const int* d_match12,
+                                   int match_stride, const orbm_pose_params* params, const int* d_maxits,
+                                   void* d_work, size_t work_bytes, int* d_n, int* d_iterations, int* d_best_inliers,
+                                   int* d_status, void* stream);
+
+orbx_status orbm_sim3_iterate_device(void* d_work, size_t work_bytes, int nsolvers, int cap,
+                                     const orbm_pose_params* params, int fix_scale, int min_inliers, int nit,
+                                     const int* d_rand, const int* d_rand_off, int* d_iterations, int* d_best_inliers,
+                                     float* d_sim3, uint8_t* d_inliers12, uint8_t* d_already2, int* d_ninliers,
+                                     int* d_nomore, int* d_used, void* stream);
+
+/* One pair on host arrays, on HIP device `device`; synchronous: the constructor, SetRansacParameters(probability,
+ * min_inliers, max_iterations) and one iterate(nit) that starts from *iterations and *best_inliers (0, 0 for a new
+ * solver; both are updated).  KeyFrame 1: kps1, kf_mp1, n1, T1w (12 floats); likewise KeyFrame 2; they count as
+ * slots 0 and 1 in the observations.  match12: n1 ints; rand: 3 * nit ints.  Outputs: *n, sim3 (13 floats),
+ * inliers12 (n1 bytes), already2 (n2 bytes), *ninliers, *nomore, *used, *status; of an invalid solver only *status
+ * is written. */
+orbx_status orbm_sim3_solve(int device, const orbx_keypoint* kps1, const int* kf_mp1, int n1, const float* T1w,
+                            const orbx_keypoint* kps2, const int* kf_mp2, int n2, const float* T2w,
+                            const orbm_map_point* pts, int nmp, const int* obs_ptr, const orbm_observation* obs,
+                            const uint8_t* obs_erased, const int* match12, const orbm_pose_params* params,
+                            int fix_scale, double probability, int min_inliers, int max_iterations, int nit,
+                            const int* rand, int* iterations, int* best_inliers, int* n, float* sim3,
+                            uint8_t* inliers12, uint8_t* already2, int* ninliers, int* nomore, int* used, int* status);
+
+/* Test hooks, not part of the interface a caller builds on (they may change or go without notice).
+ * orbm_sim3_solve_host: the kernels' own code compiled for the CPU and run by one lane, the arguments and results of
+ * orbm_sim3_solve without a device; tests/test_sim3_solver.py compares it with its restatement bit for bit. */
+orbx_status orbm_sim3_solve_host(const orbx_keypoint* kps1, const int* kf_mp1, int n1, const float* T1w,
+                                 const orbx_keypoint* kps2, const int* kf_mp2, int n2, const float* T2w,
+                                 const orbm_map_point* pts, int nmp, const int* obs_ptr, const orbm_observation* obs,
+                                 const uint8_t* obs_erased, const int* match12, const orbm_pose_params* params,
+                                 int fix_scale, double probability, int min_inliers, int max_iterations, int nit,
+                                 const int* rand, int* iterations, int* best_inliers, int* n, float* sim3,
+                                 uint8_t* inliers12, uint8_t* already2, int* ninliers, int* nomore, int* used,
+                                 int* status);
+
+/* Test hook: atan2 as the Sim3 solver evaluates it (csrc/orbx_math.hpp fixed_atan2). */
+double orbx_fixed_atan2(double y, double x);
+
+/* Test hook: the three correspondences iteration draws r[0..2] select among n (RandomInt and the removal). */
+void orbx_sim3_triplet(int n, const int* r, int* out3);
+
 /* ---- New MapPoints: the match loop of LocalMapping::CreateNewMapPoints ----
  * src/LocalMapping.cc:284-450, between SearchForTriangulation (orbm_bow_search_device, ORBM_TRIANGULATION) and the
  * MapPoint refresh above.  For every vMatchedPairs entry: the parallax of the two rays, a 4x4 cv::SVD triangulation

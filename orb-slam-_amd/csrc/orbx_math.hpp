@@ -152,6 +152,85 @@ ORBX_HD void po_sincos_theta3(double th, double* sinv, double* cosv, double* th3
     }
 }
 
+// atan2(y, x) in double for the Sim3 solver's quaternion angle (DESIGN.md §3 "Sim3 solver arithmetic"): a fixed
+// sequence of double + - * / and comparisons that the host and the gfx950 code evaluate alike, for the same reason as
+// po_sincos_theta3.  The published fdlibm scheme: atan by reduction to one of five intervals (breakpoints 7/16,
+// 11/16, 19/16, 39/16) with a two-part atan(0.5), atan(1), atan(1.5), atan(inf) and the degree-11 minimax
+// polynomial in z = x*x split into odd and even halves; atan2 by quadrant with a two-part pi.  The exponent tests of
+// fdlibm are comparisons of values here (|x| < 2^-29, |x| >= 2^66, |y/x| beyond 2^+-60 decided on the quotient), so
+// inputs whose quotient over- or underflows take the limit branch.  Within 1 ulp of glibc (tests/test_sim3_solver.py).
+constexpr double kAT_hi0 = 4.63647609000806093515e-01, kAT_hi1 = 7.85398163397448278999e-01,
+                 kAT_hi2 = 9.82793723247329054082e-01, kAT_hi3 = 1.57079632679489655800e+00;
+constexpr double kAT_lo0 = 2.26987774529616870924e-17, kAT_lo1 = 3.06161699786838301793e-17,
+                 kAT_lo2 = 1.39033110312309984516e-17, kAT_lo3 = 6.12323399573676603587e-17;
+constexpr double kAT_0 = 3.33333333333329318027e-01, kAT_1 = -1.99999999998764832476e-01,
+                 kAT_2 = 1.42857142725034663711e-01, kAT_3 = -1.11111104054623557880e-01,
+                 kAT_4 = 9.09088713343650656196e-02, kAT_5 = -7.69187620504482999495e-02,
+                 kAT_6 = 6.66107313738753120669e-02, kAT_7 = -5.83357013379057348645e-02,
+                 kAT_8 = 4.97687799461593236017e-02, kAT_9 = -3.65315727442169155270e-02,
+                 kAT_10 = 1.62858201153657823623e-02;
+constexpr double kAT_pi = 3.1415926535897931160e+00, kAT_pi_lo = 1.2246467991473531772e-16;
+
+// atan(x), x >= 0 and not NaN
+ORBX_HD double fixed_atan_pos(double x)
+{
+    if (x >= 73786976294838206464.0) return kAT_hi3 + kAT_lo3;   // 2^66
+    if (x < 0.4375) {
+        if (x < 1.862645149230957e-09) return x;                 // 2^-29
+        const double z = x * x, w = z * z;
+        const double s1 = z * (kAT_0 + w * (kAT_2 + w * (kAT_4 + w * (kAT_6 + w * (kAT_8 + w * kAT_10)))));
+        const double s2 = w * (kAT_1 + w * (kAT_3 + w * (kAT_5 + w * (kAT_7 + w * kAT_9))));
+        return x - x * (s1 + s2);
+    }
+    double hi, lo;
+    if (x < 1.1875) {
+        if (x < 0.6875) {
+            hi = kAT_hi0; lo = kAT_lo0;
+            x = (2.0 * x - 1.0) / (2.0 + x);
+        } else {
+            hi = kAT_hi1; lo = kAT_lo1;
+            x = (x - 1.0) / (x + 1.0);
+        }
+    } else if (x < 2.4375) {
+        hi = kAT_hi2; lo = kAT_lo2;
+        x = (x - 1.5) / (1.0 + 1.5 * x);
+    } else {
+        hi = kAT_hi3; lo = kAT_lo3;
+        x = -1.0 / x;
+    }
+    const double z = x * x, w = z * z;
+    const double s1 = z * (kAT_0 + w * (kAT_2 + w * (kAT_4 + w * (kAT_6 + w * (kAT_8 + w * kAT_10)))));
+    const double s2 = w * (kAT_1 + w * (kAT_3 + w * (kAT_5 + w * (kAT_7 + w * kAT_9))));
+    return hi - ((x * (s1 + s2) - lo) - x);
+}
+
+ORBX_HD double fixed_atan2(double y, double x)
+{
+    if (x != x || y != y) return x + y;
+    const bool xneg = x < 0.0 || (x == 0.0 && 1.0 / x < 0.0);
+    const bool yneg = y < 0.0 || (y == 0.0 && 1.0 / y < 0.0);
+    const double pio2 = kAT_hi3 + 0.5 * kAT_pi_lo;
+    if (y == 0.0) {
+        if (!xneg) return y;                          // atan2(+-0, +anything) = +-0
+        return yneg ? -kAT_pi : kAT_pi;
+    }
+    if (x == 0.0) return yneg ? -pio2 : pio2;
+    const double ax = xneg ? -x : x, ay = yneg ? -y : y;
+    const double inf = __builtin_inf();
+    double z;
+    if (ax == inf) {
+        z = ay == inf ? (xneg ? 3.0 * kAT_hi1 : kAT_hi1) : (xneg ? kAT_pi : 0.0);
+        return yneg ? -z : z;
+    }
+    if (ay == inf) return yneg ? -pio2 : pio2;
+    const double q = ay / ax;
+    if (q > 1152921504606846976.0) z = pio2;                       // 2^60
+    else if (xneg && q < 8.673617379884035e-19) z = 0.0;           // 2^-60
+    else z = fixed_atan_pos(q);
+    if (!xneg) return yneg ? -z : z;
+    return yneg ? (z - kAT_pi_lo) - kAT_pi : kAT_pi - (z - kAT_pi_lo);
+}
+
 // (float)(CV_PI/180.f), src/ORBextractor.cc:131
 constexpr float kFactorPI = (float)(3.1415926535897932384626433832795 / 180.f);
 

@@ -2,6 +2,7 @@
 // lists and plain types standing in for cv::Mat / cv::KeyPoint / the ORB-SLAM2 objects.  Built (not run)
 // by the Makefile, so a snippet that drifts from include/orbx.h breaks the build.
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 #include "../../include/orbx.h"
@@ -342,6 +343,47 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     orbm_compact_observations(0, obs_ptr.data(), obs.data(), obs_erased.data(), np, obs_ptr_out.data(), obs_out.data(),
                               &compact_status);
     if (mp_verdict[0] == ORBM_CULL_INVALID || kf_verdict[0] == ORBM_KFCULL_INVALID) nlocal = 0;
+
+    // LoopClosing::ComputeSim3: SearchByBoW(KF, KF) -> Sim3Solver -> SearchBySim3 on one stream
+    const orbm_bow_view *d_view_cur = nullptr, *d_view_cand = nullptr;   // one row per candidate
+    const int *d_cand_a = nullptr, *d_cand_b = nullptr, *d_rand = nullptr, *d_rand_off = nullptr;
+    const uint8_t* d_mpdesc = nullptr;
+    int ncands3 = 8, max_nodes1 = 1000;
+    int *d_bow12 = nullptr, *d_nbow = nullptr, *d_s3_n = nullptr, *d_s3_its = nullptr, *d_s3_best = nullptr;
+    int *d_s3_status = nullptr, *d_s3_ninl = nullptr, *d_s3_nomore = nullptr, *d_s3_used = nullptr;
+    int *d_s3_match12 = nullptr, *d_s3_nfound = nullptr;
+    float* d_sim3 = nullptr;
+    uint8_t *d_inliers12 = nullptr, *d_already2 = nullptr;
+    std::vector<int> maxits((size_t)cap + 1);   // mRansacMaxIts per N, once per parameter set; copied to d_maxits
+    for (int k = 0; k <= cap; k++) maxits[k] = orbm_sim3_ransac_iterations(k, 0.99, 20, 300);
+    const int* d_maxits = nullptr;
+    size_t s3_bytes = orbm_sim3_workspace_bytes(ncands3, cap, 5);
+    void* d_s3_work = nullptr;   // hipMalloc once
+    orbm_bow_search_device(ORBM_BOW_KF_KF, d_view_cur, d_view_cand, nullptr, ncands3, max_nodes1, 0.75f, 1, d_bow12, cap,
+                           d_nbow, stream);
+    orbm_sim3_setup_device(d_kps_un, d_counts, nkf, cap, d_Tcw, d_kf_mp, d_mps_rw, nmp, d_obs_ptr, d_obs, d_obs_erased,
+                           d_cand_a, d_cand_b, ncands3, d_bow12, cap, &P, d_maxits, d_s3_work, s3_bytes, d_s3_n,
+                           d_s3_its, d_s3_best, d_s3_status, stream);
+    // one round of the while loop (:286-342): five iterations of every candidate still in play
+    orbm_sim3_iterate_device(d_s3_work, s3_bytes, ncands3, cap, &P, /*mbFixScale*/ 0, 20, 5, d_rand, d_rand_off,
+                             d_s3_its, d_s3_best, d_sim3, d_inliers12, d_already2, d_s3_ninl, d_s3_nomore, d_s3_used,
+                             stream);
+    orbm_search_by_sim3_device(d_kps_un, d_desc, d_mps_rw, d_mpdesc, d_counts, nkf, cap, d_Tcw, d_cand_a, d_cand_b,
+                               d_sim3, d_inliers12, d_already2, ncands3, &P, d_s3_match12, d_s3_nfound, nullptr,
+                               nullptr, stream);
+    // ... and one candidate on host arrays: a new solver's first five iterations
+    {
+        std::vector<int> mp1(n, -1), mp2(n, -1), bow12(n, -1), draws(15);
+        std::vector<uint8_t> inl12(n), alr2(n);
+        for (int& r : draws) r = rand();
+        int its = 0, best = 0, N = 0, nInliers = 0, bNoMore = 0, used = 0, s3_status = 0;
+        float sim3[13];
+        orbm_sim3_solve(0, (const orbx_keypoint*)kps.data(), mp1.data(), n, T1w, (const orbx_keypoint*)kps.data(),
+                        mp2.data(), n, T2w, mps.data(), np, obs_ptr.data(), obs.data(), obs_erased.data(), bow12.data(),
+                        &P, 0, 0.99, 20, 300, 5, draws.data(), &its, &best, &N, sim3, inl12.data(), alr2.data(),
+                        &nInliers, &bNoMore, &used, &s3_status);
+        if (s3_status & ORBM_SIM3_INVALID) nInliers = 0;
+    }
 
     // ComputeBoW
     std::vector<int32_t> bw(n), node(n), ptr(n + 1), idx(n);

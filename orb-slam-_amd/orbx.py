@@ -50,6 +50,8 @@ EXPORTED = [
     "orbx_rgbd_stereo", "orbm_frustum_batch_device", "orbm_frustum",
     "orbm_pose_optimization_device", "orbm_pose_optimization", "orbm_pose_optimization_host",
     "orbx_po_sincos_theta3",
+    "orbm_sim3_workspace_bytes", "orbm_sim3_ransac_iterations", "orbm_sim3_setup_device", "orbm_sim3_iterate_device",
+    "orbm_sim3_solve", "orbm_sim3_solve_host", "orbx_fixed_atan2", "orbx_sim3_triplet",
     "orbm_refresh_map_points_device", "orbm_refresh_map_points", "orbm_triangulate_device", "orbm_triangulate",
     "orbm_local_map_work_bytes", "orbm_local_map_device", "orbm_local_map",
     "orbm_connections_work_bytes", "orbm_update_connections_device", "orbm_update_connections",
@@ -285,6 +287,21 @@ def _load():
             vp, vp, C.c_int, vp, vp, C.c_int, vp, P(PoseParams), C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_po_sincos_theta3.argtypes = [C.c_double, C.POINTER(C.c_double)]
     L.orbx_po_sincos_theta3.restype = None
+    L.orbm_sim3_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.orbm_sim3_workspace_bytes.restype = C.c_size_t
+    L.orbm_sim3_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int]
+    L.orbm_sim3_setup_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp,
+                                         C.c_int, P(PoseParams), vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.orbm_sim3_iterate_device.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, P(PoseParams), C.c_int, C.c_int, C.c_int,
+                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    for fn in (L.orbm_sim3_solve, L.orbm_sim3_solve_host):
+        fn.argtypes = ([C.c_int] if fn is L.orbm_sim3_solve else []) + [
+            vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, P(PoseParams), C.c_int, C.c_double,
+            C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_fixed_atan2.argtypes = [C.c_double, C.c_double]
+    L.orbx_fixed_atan2.restype = C.c_double
+    L.orbx_sim3_triplet.argtypes = [C.c_int, i32p, i32p]
+    L.orbx_sim3_triplet.restype = None
     L.orbm_refresh_map_points_device.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int,
                                                  C.c_int, P(PoseParams), vp, vp, vp, vp]
     L.orbm_refresh_map_points.argtypes = [C.c_int, C.c_int, vp, u8p, i32p, C.c_int, C.c_int, f32p, u8p, i32p, vp, vp,
@@ -788,6 +805,128 @@ def po_sincos_theta3(theta):
     o = (C.c_double * 3)()
     lib.orbx_po_sincos_theta3(float(theta), o)
     return o[0], o[1], o[2]
+
+
+SIM3_INVALID = 1    # orbm_sim3_*: status bits
+
+
+def sim3_ransac_iterations(n, probability=0.99, min_inliers=20, max_iterations=300):
+    """mRansacMaxIts of Sim3Solver::SetRansacParameters for N = n (src/Sim3Solver.cc:125-135)."""
+    return lib.orbm_sim3_ransac_iterations(int(n), float(probability), int(min_inliers), int(max_iterations))
+
+
+def fixed_atan2(y, x):
+    """atan2 as the Sim3 solver evaluates it (host code)."""
+    return lib.orbx_fixed_atan2(float(y), float(x))
+
+
+def sim3_triplet(n, draws):
+    """The three correspondences one iteration's raw rand() draws select among n (RandomInt and the removal)."""
+    r = np.ascontiguousarray(draws, np.int32).reshape(3)
+    o = np.zeros(3, np.int32)
+    lib.orbx_sim3_triplet(int(n), r.ctypes.data_as(C.POINTER(C.c_int)), o.ctypes.data_as(C.POINTER(C.c_int)))
+    return [int(v) for v in o]
+
+
+def sim3_solve(kf1, kf2, T1w, T2w, pts, obs_ptr, obs, match12, rand, params, nit, obs_erased=None, fix_scale=False,
+               probability=0.99, min_inliers=20, max_iterations=300, iterations=0, best_inliers=0, device=0,
+               on_host=False):
+    """Sim3Solver on host arrays (one pair): the constructor, SetRansacParameters and one iterate(nit) that starts
+    from (iterations, best_inliers).  kf = (mvKeysUn KEYPOINT_DTYPE, GetMapPointMatches() as int32 rows of pts, -1
+    none); KeyFrame 1 is slot 0 and KeyFrame 2 slot 1 in obs; T1w / T2w 3x4 Tcw; pts MAP_POINT_DTYPE; obs_ptr
+    (nmp + 1,), obs OBSERVATION_DTYPE, obs_erased uint8 or None; match12 (n1,) int32 as SearchByBoW leaves it; rand:
+    at least 3 * nit raw rand() values.  on_host=True runs the kernels' code on the CPU (orbm_sim3_solve_host).
+    Returns a dict: status, and for a valid solver n, sim3 (13,) float32 = s12, R12, t12 (zeros without a result),
+    inliers12 (n1,) uint8, already2 (n2,) uint8, ninliers, nomore, used, iterations, best_inliers."""
+    k1, k2 = (np.ascontiguousarray(kf[0], KEYPOINT_DTYPE) for kf in (kf1, kf2))
+    m1, m2 = (np.ascontiguousarray(kf[1], np.int32).reshape(-1) for kf in (kf1, kf2))
+    n1, n2 = len(k1), len(k2)
+    assert len(m1) == n1 and len(m2) == n2
+    p = np.ascontiguousarray(pts, MAP_POINT_DTYPE).reshape(-1)
+    op = np.ascontiguousarray(obs_ptr, np.int32).reshape(-1)
+    ob = np.ascontiguousarray(obs, OBSERVATION_DTYPE).reshape(-1)
+    er = None if obs_erased is None else np.ascontiguousarray(obs_erased, np.uint8).reshape(-1)
+    assert len(op) == len(p) + 1 and (er is None or len(er) == len(ob))
+    m12 = np.ascontiguousarray(match12, np.int32).reshape(-1)
+    rd = np.ascontiguousarray(rand, np.int32).reshape(-1)
+    assert len(m12) == n1 and len(rd) >= 3 * nit
+    t1, t2 = (np.ascontiguousarray(np.asarray(T, np.float32).reshape(-1)[:12]) for T in (T1w, T2w))
+    sim3 = np.zeros(13, np.float32)
+    in12, al2 = np.zeros(max(n1, 1), np.uint8), np.zeros(max(n2, 1), np.uint8)
+    ints = [C.c_int(v) for v in (iterations, best_inliers, 0, 0, 0, 0, 0)]
+    iv = [C.cast(C.byref(v), C.c_void_p) for v in ints]
+    d = lambda a: a.ctypes.data if a is not None and len(a) else None   # noqa: E731
+    prm = PoseParams.from_buffer_copy(params)
+    args = (d(k1), d(m1), n1, t1.ctypes.data, d(k2), d(m2), n2, t2.ctypes.data, d(p), len(p),
+            op.ctypes.data if len(p) else None, d(ob), d(er), d(m12), C.byref(prm), int(bool(fix_scale)),
+            float(probability), int(min_inliers), int(max_iterations), int(nit), rd.ctypes.data, iv[0], iv[1], iv[2],
+            sim3.ctypes.data, in12.ctypes.data, al2.ctypes.data, iv[3], iv[4], iv[5], iv[6])
+    if on_host:
+        _check("orbm_sim3_solve_host", lib.orbm_sim3_solve_host(*args))
+    else:
+        _check("orbm_sim3_solve", lib.orbm_sim3_solve(device, *args))
+    if ints[6].value:
+        return dict(status=ints[6].value)
+    return dict(status=0, n=ints[2].value, sim3=sim3, inliers12=in12[:n1], already2=al2[:n2], ninliers=ints[3].value,
+                nomore=ints[4].value, used=ints[5].value, iterations=ints[0].value, best_inliers=ints[1].value)
+
+
+class Sim3Solver:
+    """A batch of ORB_SLAM2::Sim3Solver on the device: one solver per KeyFrame pair, kept in a workspace between
+    the calls.  setup() is the constructor and SetRansacParameters, iterate(nit, ...) the reference's iterate of every
+    solver, find(...) an iterate over all of mRansacMaxIts.  Tensors live on the device of `kps`."""
+
+    def __init__(self, nsolvers, cap, max_iters_per_call, params, device, probability=0.99, min_inliers=20,
+                 max_iterations=300, fix_scale=False):
+        import torch
+        self.nsolvers, self.cap, self.max_iters = int(nsolvers), int(cap), int(max_iters_per_call)
+        self.params = PoseParams.from_buffer_copy(params)
+        self.min_inliers, self.max_iterations, self.fix_scale = int(min_inliers), int(max_iterations), bool(fix_scale)
+        self.work_bytes = lib.orbm_sim3_workspace_bytes(self.nsolvers, self.cap, self.max_iters)
+        if not self.work_bytes and self.nsolvers:
+            raise OrbxError("orbm_sim3_workspace_bytes", EINVAL)
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)   # noqa: E731
+        self.work = torch.zeros((max(self.work_bytes, 16) + 7) // 8, dtype=torch.int64, device=device)
+        table = [sim3_ransac_iterations(n, probability, min_inliers, max_iterations) for n in range(self.cap + 1)]
+        self.maxits = torch.tensor(table, dtype=torch.int32, device=device)
+        self.n, self.iterations, self.best_inliers, self.status = (i32(self.nsolvers) for _ in range(4))
+        self.sim3 = torch.zeros((self.nsolvers, 13), dtype=torch.float32, device=device)
+        self.inliers12 = torch.zeros((self.nsolvers, self.cap), dtype=torch.uint8, device=device)
+        self.already2 = torch.zeros((self.nsolvers, self.cap), dtype=torch.uint8, device=device)
+        self.ninliers, self.nomore, self.used = (i32(self.nsolvers) for _ in range(3))
+
+    def setup(self, kps, counts, pose, kf_mp, pts, obs_ptr, obs, pair_a, pair_b, match12, obs_erased=None,
+              stream=None):
+        """kps (B, cap, 7) int32, counts (B,), pose (B, 12) float32, kf_mp (B, cap) int32, pts (nmp, 12) int32 view of
+        MAP_POINT_DTYPE, obs_ptr (nmp + 1,), obs (nobs, 2) int32, pair_a / pair_b (nsolvers,), match12 (nsolvers,
+        stride) int32 as bow_search leaves it.  Writes n, iterations = best_inliers = 0 and status."""
+        assert kps.shape[1] == self.cap and pair_a.shape[0] == self.nsolvers and match12.shape[0] == self.nsolvers
+        _check("orbm_sim3_setup_device",
+               lib.orbm_sim3_setup_device(_ptr(kps), _ptr(counts), kps.shape[0], self.cap, _ptr(pose), _ptr(kf_mp),
+                                          _ptr(pts), pts.shape[0], _ptr(obs_ptr), _ptr(obs),
+                                          _ptr(obs_erased) if obs_erased is not None else None, _ptr(pair_a),
+                                          _ptr(pair_b), self.nsolvers, _ptr(match12), match12.shape[1],
+                                          C.byref(self.params), _ptr(self.maxits), _ptr(self.work), self.work_bytes,
+                                          _ptr(self.n), _ptr(self.iterations), _ptr(self.best_inliers),
+                                          _ptr(self.status), _stream(stream)))
+        return self.n, self.status
+
+    def iterate(self, nit, rand, rand_off, stream=None):
+        """iterate(nit) of every solver: rand int32 raw rand() values, rand_off (nsolvers,) int32 where each solver's
+        draws start (3 per iteration).  Returns (sim3, inliers12, already2, ninliers, nomore, used); the state
+        tensors iterations / best_inliers are updated."""
+        _check("orbm_sim3_iterate_device",
+               lib.orbm_sim3_iterate_device(_ptr(self.work), self.work_bytes, self.nsolvers, self.cap,
+                                            C.byref(self.params), int(self.fix_scale), self.min_inliers, int(nit),
+                                            _ptr(rand), _ptr(rand_off), _ptr(self.iterations),
+                                            _ptr(self.best_inliers), _ptr(self.sim3), _ptr(self.inliers12),
+                                            _ptr(self.already2), _ptr(self.ninliers), _ptr(self.nomore),
+                                            _ptr(self.used), _stream(stream)))
+        return self.sim3, self.inliers12, self.already2, self.ninliers, self.nomore, self.used
+
+    def find(self, rand, rand_off, stream=None):
+        """Sim3Solver::find: iterate(mRansacMaxIts); needs max_iters_per_call >= max_iterations."""
+        return self.iterate(self.max_iterations, rand, rand_off, stream)
 
 
 def refresh_map_points_device(what, kps, desc, counts, pose, kf_bad, obs_ptr, obs, ref, max_obs, params, pts, pdesc,
