@@ -1121,21 +1121,16 @@ orbx_status orbx_compute_stereo_matches(orbx_handle* left, orbx_handle* right, c
     if (cap > 32767) return ORBX_EINVAL;
     HostCall c(left->device);
     const int hmeta[5] = {n_l, n_r, 0, 1, 0};   // counts[2], fl, fr, ngood
-    const size_t om = c.in(hmeta, sizeof(hmeta));
+    const auto om = c.in(hmeta, 5);
     // the kernels address frame f's keypoints at kps + f * cap: left rows at 0, right rows at cap
-    const size_t ok = c.in(nullptr, sizeof(orbx_keypoint) * 2 * (size_t)cap);
-    const size_t od = c.in(nullptr, (size_t)64 * cap);
-    const size_t ou = c.out(sizeof(float) * (size_t)cap), oz = c.out(sizeof(float) * (size_t)cap);
-    const size_t osad = c.out(sizeof(int) * (size_t)cap);
+    const auto ok = c.stage<orbx_keypoint>(2 * (size_t)cap);
+    const auto od = c.stage<uint8_t>((size_t)64 * cap);
+    const auto ou = c.out<float>((size_t)cap), oz = c.out<float>((size_t)cap);
+    const auto osad = c.out<int>((size_t)cap);
     orbx_status st = c.prepare();
     if (st != ORBX_OK) return st;
-    uint8_t* hk = c.host(ok);
-    uint8_t* hd = c.host(od);
-    if (!hk || !hd) return ORBX_ENOMEM;
-    std::memcpy(hk, kps_l, sizeof(orbx_keypoint) * (size_t)n_l);
-    if (n_r > 0) std::memcpy(hk + sizeof(orbx_keypoint) * (size_t)cap, kps_r, sizeof(orbx_keypoint) * (size_t)n_r);
-    std::memcpy(hd, desc_l, (size_t)32 * n_l);
-    if (n_r > 0) std::memcpy(hd + (size_t)32 * cap, desc_r, (size_t)32 * n_r);
+    pack_pair(c.host(ok), (size_t)cap, kps_l, (size_t)n_l, kps_r, (size_t)n_r);
+    pack_pair(c.host(od), (size_t)32 * cap, desc_l, (size_t)32 * n_l, desc_r, (size_t)32 * n_r);
     if ((st = c.upload()) != ORBX_OK) return st;
     // the two images' pyramids: written by each handle's last extraction, on whatever stream it ran
     order_after_last(left, c.stream());
@@ -1147,15 +1142,13 @@ orbx_status orbx_compute_stereo_matches(orbx_handle* left, orbx_handle* right, c
     float maxD;
     int rband;
     stereo_limits(left, bf, fx, &maxD, &rband);
-    int* meta = c.dev_as<int>(om);
-    launch_stereo(left->geom, left->d_geom, PL, PR, c.dev_as<orbx_keypoint>(ok), c.dev(od), meta, cap, meta + 2,
-                  meta + 3, 1, bf, maxD, rband, c.dev_as<float>(ou), c.dev_as<float>(oz), c.dev_as<int>(osad),
-                  meta + 4, c.stream());
+    launch_stereo(left->geom, left->d_geom, PL, PR, c.dev(ok), c.dev(od), c.dev(om), cap, c.dev(om, 2), c.dev(om, 3),
+                  1, bf, maxD, rband, c.dev(ou), c.dev(oz), c.dev(osad), c.dev(om, 4), c.stream());
     if (hipGetLastError() != hipSuccess) return ORBX_EDEVICE;
     int ng = 0;
-    c.fetch(ou, u_right, sizeof(float) * (size_t)n_l);
-    c.fetch(oz, depth, sizeof(float) * (size_t)n_l);
-    c.fetch(om + 16, &ng, sizeof(int));
+    c.fetch(ou, u_right, (size_t)n_l);
+    c.fetch(oz, depth, (size_t)n_l);
+    c.fetch(om, &ng, 1, 4);
     if ((st = c.finish()) != ORBX_OK) return st;
     *n_good = ng;
     return ORBX_OK;
@@ -1220,37 +1213,38 @@ bool bow_view_ok(const orbm_bow_view* v)
     return v->fv_nnodes == 0 || v->fv_ptr[0] == 0;
 }
 
-// offsets of one staged view (device pointers are patched in after the buffers are sized)
-struct BowOffs {
-    size_t kps, desc, mp, ur, node, ptr, idx;
-    bool has_mp, has_ur;
+// blocks of one staged view (device pointers are patched in after the buffers are sized)
+struct BowBlks {
+    Blk<orbx_keypoint> kps;
+    Blk<uint8_t> desc, mp;
+    Blk<float> ur;
+    Blk<int32_t> node, ptr, idx;
 };
 
-BowOffs bow_stage(HostCall& c, const orbm_bow_view* v)
+BowBlks bow_stage(HostCall& c, const orbm_bow_view* v)
 {
-    BowOffs o;
-    o.kps = c.in(v->kps, sizeof(orbx_keypoint) * (size_t)v->n);
-    o.desc = c.in(v->desc, (size_t)32 * v->n);
-    o.has_mp = v->has_mp != nullptr;
-    o.has_ur = v->u_right != nullptr;
-    o.mp = o.has_mp ? c.in(v->has_mp, (size_t)v->n) : 0;
-    o.ur = o.has_ur ? c.in(v->u_right, sizeof(float) * (size_t)v->n) : 0;
-    o.node = c.in(v->fv_node, sizeof(int32_t) * (size_t)v->fv_nnodes);
-    o.ptr = c.in(v->fv_ptr, sizeof(int32_t) * ((size_t)v->fv_nnodes + 1));
-    o.idx = c.in(v->fv_idx, sizeof(int32_t) * (size_t)(v->fv_nnodes ? v->fv_ptr[v->fv_nnodes] : 0));
+    const size_t n = (size_t)v->n, nn = (size_t)v->fv_nnodes;
+    BowBlks o;
+    o.kps = c.in(v->kps, n);
+    o.desc = c.in(v->desc, 32 * n);
+    if (v->has_mp) o.mp = c.in(v->has_mp, n);
+    if (v->u_right) o.ur = c.in(v->u_right, n);
+    o.node = c.in(v->fv_node, nn);
+    o.ptr = c.in(v->fv_ptr, nn + 1);
+    o.idx = c.in(v->fv_idx, (size_t)(nn ? v->fv_ptr[nn] : 0));
     return o;
 }
 
-orbm_bow_view bow_device_view(uint8_t* base, const BowOffs& o, const orbm_bow_view* v)
+orbm_bow_view bow_device_view(const HostCall& c, const BowBlks& o, const orbm_bow_view* v)
 {
     orbm_bow_view d = *v;
-    d.kps = (const orbx_keypoint*)(base + o.kps);
-    d.desc = base + o.desc;
-    d.has_mp = o.has_mp ? base + o.mp : nullptr;
-    d.u_right = o.has_ur ? (const float*)(base + o.ur) : nullptr;
-    d.fv_node = (const int32_t*)(base + o.node);
-    d.fv_ptr = (const int32_t*)(base + o.ptr);
-    d.fv_idx = (const int32_t*)(base + o.idx);
+    d.kps = c.dev(o.kps);
+    d.desc = c.dev(o.desc);
+    d.has_mp = v->has_mp ? c.dev(o.mp) : nullptr;
+    d.u_right = v->u_right ? c.dev(o.ur) : nullptr;
+    d.fv_node = c.dev(o.node);
+    d.fv_ptr = c.dev(o.ptr);
+    d.fv_idx = c.dev(o.idx);
     return d;
 }
 
@@ -1270,24 +1264,20 @@ orbx_status orbm_bow_search(int device, int mode, const orbm_bow_view* view1, co
     if (nout == 0) return ORBX_OK;
     HostCall c(device);
     // the two device view structs (+ tp) first: they are patched after the buffers are sized
-    const size_t ov = c.in(nullptr, 2 * sizeof(orbm_bow_view) + sizeof(orbm_triang_params));
-    const BowOffs o1 = bow_stage(c, view1), o2 = bow_stage(c, view2);
-    const size_t om = c.out(sizeof(int) * ((size_t)nout + 1));
+    const auto ov = c.stage<orbm_bow_view>(2);
+    const auto otp = c.in(tp, tp ? 1 : 0);
+    const BowBlks o1 = bow_stage(c, view1), o2 = bow_stage(c, view2);
+    const auto om = c.out<int>((size_t)nout + 1);   // nmatches, match
     orbx_status rc = c.prepare();
     if (rc != ORBX_OK) return rc;
-    uint8_t* base = c.dev(0);
-    orbm_bow_view dv[2] = {bow_device_view(base, o1, view1), bow_device_view(base, o2, view2)};
-    std::memcpy(c.host(ov), dv, sizeof(dv));
-    if (tp) std::memcpy(c.host(ov) + sizeof(dv), tp, sizeof(*tp));
+    c.host(ov)[0] = bow_device_view(c, o1, view1);
+    c.host(ov)[1] = bow_device_view(c, o2, view2);
     if ((rc = c.upload()) != ORBX_OK) return rc;
-    const orbm_bow_view* d1 = c.dev_as<const orbm_bow_view>(ov);
-    const orbm_triang_params* dtp = (const orbm_triang_params*)(c.dev(ov) + sizeof(dv));
-    int* dm = c.dev_as<int>(om);
-    rc = orbm_bow_search_device(mode, d1, d1 + 1, dtp, 1, view1->fv_nnodes, nnratio, check_ori, dm + 1, nout, dm,
-                                c.stream());
+    rc = orbm_bow_search_device(mode, c.dev(ov), c.dev(ov, 1), c.dev(otp), 1, view1->fv_nnodes, nnratio, check_ori,
+                                c.dev(om, 1), nout, c.dev(om), c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(om + sizeof(int), match, sizeof(int) * (size_t)nout);
-    c.fetch(om, nmatches, sizeof(int));
+    c.fetch(om, match, (size_t)nout, 1);
+    c.fetch(om, nmatches, 1);
     return c.finish();
 }
 
@@ -1322,25 +1312,21 @@ orbx_status orbm_search_by_projection(int device, const orbx_keypoint* kps, cons
     if (np == 0) return ORBX_OK;
     HostCall c(device);
     const int cn[2] = {n, np};
-    const size_t ocn = c.in(cn, sizeof(cn));
-    const size_t ok = c.in(kps, sizeof(orbx_keypoint) * (size_t)n);
-    const size_t od = c.in(desc, (size_t)32 * n);
-    const size_t ou = c.in(uright, sizeof(float) * (size_t)n);
-    const size_t oc = c.in(claimed, (size_t)n);
-    const size_t op = c.in(pts, sizeof(orbm_proj_point) * (size_t)np);
-    const size_t opd = c.in(pdesc, (size_t)32 * np);
-    const size_t om = c.out(sizeof(int) * ((size_t)n + 1));
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const auto ocn = c.in(cn, 2);
+    const auto ok = c.in(kps, (size_t)n);
+    const auto od = c.in(desc, (size_t)32 * n);
+    const auto ou = c.in(uright, (size_t)n);
+    const auto oc = c.in(claimed, (size_t)n);
+    const auto op = c.in(pts, (size_t)np);
+    const auto opd = c.in(pdesc, (size_t)32 * np);
+    const auto om = c.out<int>((size_t)n + 1);   // nmatches, match
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
-    int* dm = c.dev_as<int>(om);
-    const int* dcn = c.dev_as<const int>(ocn);
-    rc = orbm_search_by_projection_device(c.dev_as<const orbx_keypoint>(ok), c.dev(od), c.dev_as<const float>(ou),
-                                          c.dev(oc), dcn, 1, n, c.dev_as<const orbm_proj_point>(op), c.dev(opd),
-                                          dcn + 1, np, params, dm + 1, dm, c.stream());
+    rc = orbm_search_by_projection_device(c.dev(ok), c.dev(od), c.dev(ou), c.dev(oc), c.dev(ocn), 1, n, c.dev(op),
+                                          c.dev(opd), c.dev(ocn, 1), np, params, c.dev(om, 1), c.dev(om), c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(om + sizeof(int), match, sizeof(int) * (size_t)n);
-    c.fetch(om, nmatches, sizeof(int));
+    c.fetch(om, match, (size_t)n, 1);
+    c.fetch(om, nmatches, 1);
     return c.finish();
 }
 
@@ -1385,27 +1371,23 @@ orbx_status orbm_project_search(int device, int mode, const orbx_keypoint* kps, 
     if (n == 0 || np == 0) return ORBX_OK;
     HostCall c(device);
     const int cn[2] = {n, np};
-    const size_t ocn = c.in(cn, sizeof(cn));
-    const size_t opo = c.in(pose, sizeof(float) * 24);
-    const size_t ok = c.in(kps, sizeof(orbx_keypoint) * (size_t)n);
-    const size_t od = c.in(desc, (size_t)32 * n);
-    const size_t ou = c.in(uright, sizeof(float) * (size_t)n);
-    const size_t oc = c.in(search ? claimed : nullptr, (size_t)n);
-    const size_t op = c.in(pts, sizeof(orbm_map_point) * (size_t)np);
-    const size_t opd = c.in(pdesc, (size_t)32 * np);
-    const size_t om = c.out(sizeof(int) * ((size_t)nout + 1));
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const auto ocn = c.in(cn, 2);
+    const auto opo = c.in(pose, 24);
+    const auto ok = c.in(kps, (size_t)n);
+    const auto od = c.in(desc, (size_t)32 * n);
+    const auto ou = c.in(uright, (size_t)n);
+    const auto oc = c.in(search ? claimed : nullptr, (size_t)n);
+    const auto op = c.in(pts, (size_t)np);
+    const auto opd = c.in(pdesc, (size_t)32 * np);
+    const auto om = c.out<int>((size_t)nout + 1);   // nmatches, match
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
-    int* dm = c.dev_as<int>(om);
-    const int* dcn = c.dev_as<const int>(ocn);
-    rc = orbm_project_search_device(mode, c.dev_as<const orbx_keypoint>(ok), c.dev(od), c.dev_as<const float>(ou),
-                                    c.dev(oc), dcn, 1, n, c.dev_as<const float>(opo),
-                                    c.dev_as<const orbm_map_point>(op), c.dev(opd), dcn + 1, np, params, dm + 1, dm,
+    rc = orbm_project_search_device(mode, c.dev(ok), c.dev(od), c.dev(ou), c.dev(oc), c.dev(ocn), 1, n, c.dev(opo),
+                                    c.dev(op), c.dev(opd), c.dev(ocn, 1), np, params, c.dev(om, 1), c.dev(om),
                                     c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(om + sizeof(int), match, sizeof(int) * (size_t)nout);
-    c.fetch(om, nmatches, sizeof(int));
+    c.fetch(om, match, (size_t)nout, 1);
+    c.fetch(om, nmatches, 1);
     return c.finish();
 }
 
@@ -1466,39 +1448,31 @@ orbx_status orbm_search_by_sim3(int device, const orbx_keypoint* kps1, const uin
     std::memcpy(geo + 25, R12, sizeof(float) * 9);
     std::memcpy(geo + 34, t12, sizeof(float) * 3);
     HostCall hc(device);
-    const size_t oh = hc.in(head, sizeof(head));
-    const size_t og = hc.in(geo, sizeof(geo));
-    const size_t ok = hc.in(nullptr, sizeof(orbx_keypoint) * 2 * c);
-    const size_t od = hc.in(nullptr, 32 * 2 * c);
-    const size_t om = hc.in(nullptr, sizeof(orbm_map_point) * 2 * c);
-    const size_t omd = hc.in(nullptr, 32 * 2 * c);
-    const size_t oa = hc.in(nullptr, 2 * c);   // already1[cap], already2[cap]
-    const size_t oo = hc.out(sizeof(int) * (3 * c + 1));   // nfound, match12, match1, match2
+    const auto oh = hc.in(head, 4);
+    const auto og = hc.in(geo, 24 + 13);
+    const auto ok = hc.stage<orbx_keypoint>(2 * c);
+    const auto od = hc.stage<uint8_t>(32 * 2 * c);
+    const auto om = hc.stage<orbm_map_point>(2 * c);
+    const auto omd = hc.stage<uint8_t>(32 * 2 * c);
+    const auto oa = hc.stage<uint8_t>(2 * c);    // already1[cap], already2[cap]
+    const auto oo = hc.out<int>(3 * c + 1);      // nfound, match12, match1, match2
     orbx_status rc = hc.prepare();
     if (rc != ORBX_OK) return rc;
-    auto pack = [&](size_t off, const void* a, const void* b, size_t elem) {
-        uint8_t* h = hc.host(off);
-        std::memset(h, 0, elem * 2 * c);
-        std::memcpy(h, a, elem * (size_t)n1);
-        std::memcpy(h + elem * c, b, elem * (size_t)n2);
-    };
-    pack(ok, kps1, kps2, sizeof(orbx_keypoint));
-    pack(od, desc1, desc2, 32);
-    pack(om, mps1, mps2, sizeof(orbm_map_point));
-    pack(omd, mpdesc1, mpdesc2, 32);
-    pack(oa, already1, already2, 1);
+    const size_t m1 = (size_t)n1, m2 = (size_t)n2;
+    pack_pair(hc.host(ok), c, kps1, m1, kps2, m2);
+    pack_pair(hc.host(od), 32 * c, desc1, 32 * m1, desc2, 32 * m2);
+    pack_pair(hc.host(om), c, mps1, m1, mps2, m2);
+    pack_pair(hc.host(omd), 32 * c, mpdesc1, 32 * m1, mpdesc2, 32 * m2);
+    pack_pair(hc.host(oa), c, already1, m1, already2, m2);
     if ((rc = hc.upload()) != ORBX_OK) return rc;
-    const int* dh = hc.dev_as<const int>(oh);
-    const float* dg = hc.dev_as<const float>(og);
-    int* dout = hc.dev_as<int>(oo);
-    rc = orbm_search_by_sim3_device(hc.dev_as<const orbx_keypoint>(ok), hc.dev(od), hc.dev_as<const orbm_map_point>(om),
-                                    hc.dev(omd), dh, 2, cap, dg, dh + 2, dh + 3, dg + 24, hc.dev(oa), hc.dev(oa) + c,
-                                    1, params, dout + 1, dout, dout + 1 + c, dout + 1 + 2 * c, hc.stream());
+    rc = orbm_search_by_sim3_device(hc.dev(ok), hc.dev(od), hc.dev(om), hc.dev(omd), hc.dev(oh), 2, cap, hc.dev(og),
+                                    hc.dev(oh, 2), hc.dev(oh, 3), hc.dev(og, 24), hc.dev(oa), hc.dev(oa, c), 1, params,
+                                    hc.dev(oo, 1), hc.dev(oo), hc.dev(oo, 1 + c), hc.dev(oo, 1 + 2 * c), hc.stream());
     if (rc != ORBX_OK) return rc;
-    hc.fetch(oo, nfound, sizeof(int));
-    hc.fetch(oo + sizeof(int), match12, sizeof(int) * (size_t)n1);
-    hc.fetch(oo + sizeof(int) * (1 + c), match1, sizeof(int) * (size_t)n1);
-    hc.fetch(oo + sizeof(int) * (1 + 2 * c), match2, sizeof(int) * (size_t)n2);
+    hc.fetch(oo, nfound, 1);
+    hc.fetch(oo, match12, m1, 1);
+    hc.fetch(oo, match1, m1, 1 + c);
+    hc.fetch(oo, match2, m2, 1 + 2 * c);
     return hc.finish();
 }
 
@@ -1562,21 +1536,20 @@ orbx_status orbm_best2_csr(int device, const uint8_t* q, int nq, const uint8_t* 
     for (int k = 0; k < ncand; ++k)
         if (cand_idx[k] < 0 || cand_idx[k] >= nt) return ORBX_EINVAL;
     HostCall c(device);
-    const size_t oq = c.in(q, (size_t)32 * nq);
-    const size_t ot = c.in(t, (size_t)32 * nt);
-    const size_t op = c.in(cand_ptr, sizeof(int) * ((size_t)nq + 1));
-    const size_t oi = c.in(cand_idx, sizeof(int) * (size_t)ncand);
-    const size_t oo = c.out(sizeof(int) * 3 * (size_t)nq);
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const size_t Q = (size_t)nq;
+    const auto oq = c.in(q, 32 * Q);
+    const auto ot = c.in(t, (size_t)32 * nt);
+    const auto op = c.in(cand_ptr, Q + 1);
+    const auto oi = c.in(cand_idx, (size_t)ncand);
+    const auto oo = c.out<int>(3 * Q);   // best_idx, best, second
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
-    int* o = c.dev_as<int>(oo);
-    rc = orbm_best2_csr_device(c.dev(oq), nq, c.dev(ot), nt, c.dev_as<const int>(op), c.dev_as<const int>(oi),
-                               tie_mode, o, o + nq, o + 2 * nq, c.stream());
+    rc = orbm_best2_csr_device(c.dev(oq), nq, c.dev(ot), nt, c.dev(op), c.dev(oi), tie_mode, c.dev(oo), c.dev(oo, Q),
+                               c.dev(oo, 2 * Q), c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(oo, best_idx, sizeof(int) * (size_t)nq);
-    c.fetch(oo + sizeof(int) * (size_t)nq, best, sizeof(int) * (size_t)nq);
-    c.fetch(oo + sizeof(int) * 2 * (size_t)nq, second, sizeof(int) * (size_t)nq);
+    c.fetch(oo, best_idx, Q);
+    c.fetch(oo, best, Q, Q);
+    c.fetch(oo, second, Q, 2 * Q);
     return c.finish();
 }
 
@@ -1621,27 +1594,21 @@ orbx_status orbm_stereo_band(int device, const orbx_keypoint* kps_l, const uint8
     if (stereo_band_smem(rows, cap) > 160 * 1024) return ORBX_ENOSPC;
     HostCall c(device);
     const int meta[4] = {n_l, n_r, 0, 1};   // counts[2], left frame, right frame
-    const size_t om = c.in(meta, sizeof(meta));
-    const size_t ok = c.in(nullptr, sizeof(orbx_keypoint) * 2 * (size_t)cap);   // frame f at kps + f * cap
-    const size_t od = c.in(nullptr, (size_t)64 * cap);
-    const size_t oo = c.out(sizeof(int) * 2 * (size_t)cap);
+    const size_t C = (size_t)cap;
+    const auto om = c.in(meta, 4);
+    const auto ok = c.stage<orbx_keypoint>(2 * C);   // frame f at kps + f * cap
+    const auto od = c.stage<uint8_t>(64 * C);
+    const auto oo = c.out<int>(2 * C);               // best_idx[cap], best_dist[cap]
     orbx_status rc = c.prepare();
     if (rc != ORBX_OK) return rc;
-    uint8_t* hk = c.host(ok);
-    uint8_t* hd = c.host(od);
-    if (!hk || !hd) return ORBX_ENOMEM;
-    std::memcpy(hk, kps_l, sizeof(orbx_keypoint) * (size_t)n_l);
-    if (n_r) std::memcpy(hk + sizeof(orbx_keypoint) * (size_t)cap, kps_r, sizeof(orbx_keypoint) * (size_t)n_r);
-    std::memcpy(hd, desc_l, (size_t)32 * n_l);
-    if (n_r) std::memcpy(hd + (size_t)32 * cap, desc_r, (size_t)32 * n_r);
+    pack_pair(c.host(ok), C, kps_l, (size_t)n_l, kps_r, (size_t)n_r);
+    pack_pair(c.host(od), 32 * C, desc_l, (size_t)32 * n_l, desc_r, (size_t)32 * n_r);
     if ((rc = c.upload()) != ORBX_OK) return rc;
-    const int* m = c.dev_as<const int>(om);
-    int* o = c.dev_as<int>(oo);
-    rc = orbm_stereo_band_device(c.dev_as<const orbx_keypoint>(ok), c.dev(od), m, cap, m + 2, m + 3, 1, rows, scale,
-                                 nlevels, min_d, max_d, o, o + cap, c.stream());
+    rc = orbm_stereo_band_device(c.dev(ok), c.dev(od), c.dev(om), cap, c.dev(om, 2), c.dev(om, 3), 1, rows, scale,
+                                 nlevels, min_d, max_d, c.dev(oo), c.dev(oo, C), c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(oo, best_idx, sizeof(int) * (size_t)n_l);
-    c.fetch(oo + sizeof(int) * (size_t)cap, best_dist, sizeof(int) * (size_t)n_l);
+    c.fetch(oo, best_idx, (size_t)n_l);
+    c.fetch(oo, best_dist, (size_t)n_l, C);
     return c.finish();
 }
 
@@ -1697,22 +1664,27 @@ orbx_status orbm_allpairs(int device, const uint8_t* q, int nq, const uint8_t* t
         return ORBX_OK;
     }
     HostCall c(device);
-    const size_t oq = c.in(q, (size_t)32 * nq);
-    const size_t ot = c.in(t, (size_t)32 * nt);
-    const size_t out_bytes = mode == ORBM_TOP2 ? sizeof(int) * 3 * (size_t)nq : sizeof(uint16_t) * (size_t)nq * nt;
-    const size_t oo = c.out(out_bytes);
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const bool top2 = mode == ORBM_TOP2;
+    const size_t Q = (size_t)nq, nfull = top2 ? 0 : Q * (size_t)nt;
+    const auto oq = c.in(q, 32 * Q);
+    const auto ot = c.in(t, (size_t)32 * nt);
+    const auto oo = c.out<int>(top2 ? 3 * Q : 0);   // best_idx, best, second
+    const auto of = c.out<uint16_t>(nfull);         // the other mode's block is one unused slot, and not passed on
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
-    int* o = c.dev_as<int>(oo);
-    rc = orbm_allpairs_device(c.dev(oq), nq, c.dev(ot), nt, mode, o, o + nq, o + 2 * nq, (uint16_t*)o, c.stream());
+    if (top2)
+        rc = orbm_allpairs_device(c.dev(oq), nq, c.dev(ot), nt, mode, c.dev(oo), c.dev(oo, Q), c.dev(oo, 2 * Q),
+                                  nullptr, c.stream());
+    else
+        rc = orbm_allpairs_device(c.dev(oq), nq, c.dev(ot), nt, mode, nullptr, nullptr, nullptr, c.dev(of),
+                                  c.stream());
     if (rc != ORBX_OK) return rc;
-    if (mode == ORBM_TOP2) {
-        c.fetch(oo, best_idx, sizeof(int) * (size_t)nq);
-        c.fetch(oo + sizeof(int) * (size_t)nq, best, sizeof(int) * (size_t)nq);
-        c.fetch(oo + sizeof(int) * 2 * (size_t)nq, second, sizeof(int) * (size_t)nq);
+    if (top2) {
+        c.fetch(oo, best_idx, Q);
+        c.fetch(oo, best, Q, Q);
+        c.fetch(oo, second, Q, 2 * Q);
     } else {
-        c.fetch(oo, full, out_bytes);
+        c.fetch(of, full, nfull);
     }
     return c.finish();
 }
@@ -1770,30 +1742,24 @@ orbx_status orbm_search_for_initialization(int device, const orbx_keypoint* kps1
     const int cap = std::max(n1, n2);
     HostCall c(device);
     const int meta[4] = {n1, n2, 0, 1};   // counts[2], pair (0, 1)
-    const size_t om = c.in(meta, sizeof(meta));
-    const size_t ok = c.in(nullptr, sizeof(orbx_keypoint) * 2 * (size_t)cap);   // frame f at kps + f * cap
-    const size_t od = c.in(nullptr, (size_t)64 * cap);
-    const size_t opv = c.in(prev_matched, sizeof(float) * 2 * (size_t)n1);
-    const size_t ores = c.out(sizeof(int) * ((size_t)cap + 1));
-    const size_t osc = c.out(search_init_scratch_bytes(2, 1, cap));
+    const size_t C = (size_t)cap;
+    const auto om = c.in(meta, 4);
+    const auto ok = c.stage<orbx_keypoint>(2 * C);   // frame f at kps + f * cap
+    const auto od = c.stage<uint8_t>(64 * C);
+    const auto opv = c.in(prev_matched, 2 * (size_t)n1);   // copied back after the matches, hence not inout()
+    const auto ores = c.out<int>(C + 1);             // nmatches, matches12
+    const auto osc = c.out<uint8_t>(search_init_scratch_bytes(2, 1, cap));
     orbx_status rc = c.prepare();
     if (rc != ORBX_OK) return rc;
-    uint8_t* hk = c.host(ok);
-    uint8_t* hd = c.host(od);
-    if (!hk || !hd) return ORBX_ENOMEM;
-    std::memcpy(hk, kps1, sizeof(orbx_keypoint) * (size_t)n1);
-    std::memcpy(hk + sizeof(orbx_keypoint) * (size_t)cap, kps2, sizeof(orbx_keypoint) * (size_t)n2);
-    std::memcpy(hd, desc1, (size_t)32 * n1);
-    std::memcpy(hd + (size_t)32 * cap, desc2, (size_t)32 * n2);
+    pack_pair(c.host(ok), C, kps1, (size_t)n1, kps2, (size_t)n2);
+    pack_pair(c.host(od), 32 * C, desc1, (size_t)32 * n1, desc2, (size_t)32 * n2);
     if ((rc = c.upload()) != ORBX_OK) return rc;
-    const int* m = c.dev_as<const int>(om);
-    int* res = c.dev_as<int>(ores);
-    launch_search_init(c.dev_as<const orbx_keypoint>(ok), c.dev(od), m, 2, cap, m + 2, m + 3, 1, *grid, window,
-                       nnratio, check_ori, c.dev_as<float>(opv), c.dev(osc), res + 1, res, c.stream());
+    launch_search_init(c.dev(ok), c.dev(od), c.dev(om), 2, cap, c.dev(om, 2), c.dev(om, 3), 1, *grid, window, nnratio,
+                       check_ori, c.dev(opv), c.dev(osc), c.dev(ores, 1), c.dev(ores), c.stream());
     if (hipGetLastError() != hipSuccess) return ORBX_EDEVICE;
-    c.fetch(ores + sizeof(int), matches12, sizeof(int) * (size_t)n1);
-    c.fetch(ores, nmatches, sizeof(int));
-    c.fetch(opv, prev_matched, sizeof(float) * 2 * (size_t)n1);
+    c.fetch(ores, matches12, (size_t)n1, 1);
+    c.fetch(ores, nmatches, 1);
+    c.fetch(opv, prev_matched, opv.n);
     return c.finish();
 }
 

@@ -793,54 +793,33 @@ orbx_status orbm_update_connections(int device, const orbm_covis_graph* graph, i
     const size_t wbytes = orbm_connections_work_bytes(nkf, ccap);
     const size_t K = (size_t)nkf, M = (size_t)nmp, R = K * (size_t)ccap;
     HostCall c(device);
-    // an empty table still gets a block (never read), so that every device pointer is a valid one
-    auto in = [&c](const void* src, size_t bytes) { return bytes ? c.in(src, bytes) : c.in(nullptr, 64); };
-    const size_t ocn = c.in(counts, sizeof(int) * K);
-    const size_t okm = c.in(kf_mp, sizeof(int) * K * (size_t)cap);
-    const size_t okr = in(kf_rank, kf_rank ? sizeof(int) * K : 0);
-    const size_t opt = in(pts, sizeof(orbm_map_point) * M);
-    const size_t oop = c.in(obs_ptr, sizeof(int) * (M + 1));
-    const size_t oob = in(obs, sizeof(orbm_observation) * (size_t)obs_ptr[nmp]);
-    const size_t otg = c.in(targets, sizeof(int) * (size_t)ntargets);
+    const auto ocn = c.in(counts, K);
+    const auto okm = c.in(kf_mp, K * (size_t)cap);
+    const auto okr = c.in(kf_rank, kf_rank ? K : 0);
+    const auto opt = c.in(pts, M);
+    const auto oop = c.in(obs_ptr, M + 1);
+    const auto oob = c.in(obs, (size_t)obs_ptr[nmp]);
+    const auto otg = c.in(targets, (size_t)ntargets);
     // the graph and the status go up as well: what the call does not write keeps its bits
-    const size_t ock = c.in(graph->conn_kf, sizeof(int) * R);
-    const size_t ocw = c.in(graph->conn_w, sizeof(int) * R);
-    const size_t onc = c.in(graph->nconn, sizeof(int) * K);
-    const size_t ook = c.in(graph->ord_kf, sizeof(int) * R);
-    const size_t oow = c.in(graph->ord_w, sizeof(int) * R);
-    const size_t ono = c.in(graph->nord, sizeof(int) * K);
-    const size_t opa = c.in(graph->parent, sizeof(int) * K);
-    const size_t ofi = c.in(graph->first, K);
-    const size_t ost = c.in(status, sizeof(int) * (size_t)ntargets);
-    const size_t owk = c.out(wbytes);
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const auto ock = c.inout(graph->conn_kf, R);
+    const auto ocw = c.inout(graph->conn_w, R);
+    const auto onc = c.inout(graph->nconn, K);
+    const auto ook = c.inout(graph->ord_kf, R);
+    const auto oow = c.inout(graph->ord_w, R);
+    const auto ono = c.inout(graph->nord, K);
+    const auto opa = c.inout(graph->parent, K);
+    const auto ofi = c.inout(graph->first, K);
+    const auto ost = c.inout(status, (size_t)ntargets);
+    const auto owk = c.out<uint8_t>(wbytes);
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
     if (hipMemsetAsync(c.dev(owk), 0, wbytes, c.stream()) != hipSuccess) return ORBX_EDEVICE;
-    orbm_covis_graph g;
-    g.conn_kf = c.dev_as<int32_t>(ock);
-    g.conn_w = c.dev_as<int32_t>(ocw);
-    g.nconn = c.dev_as<int32_t>(onc);
-    g.ord_kf = c.dev_as<int32_t>(ook);
-    g.ord_w = c.dev_as<int32_t>(oow);
-    g.nord = c.dev_as<int32_t>(ono);
-    g.parent = c.dev_as<int32_t>(opa);
-    g.first = c.dev(ofi);
-    rc = orbm_update_connections_device(&g, nkf, ccap, c.dev_as<const int>(ocn), c.dev_as<const int>(okm), cap,
-                                        kf_rank ? c.dev_as<const int>(okr) : nullptr,
-                                        c.dev_as<const orbm_map_point>(opt), c.dev_as<const int>(oop),
-                                        c.dev_as<const orbm_observation>(oob), nmp, c.dev_as<const int>(otg), ntargets,
-                                        th, root, c.dev_as<int>(ost), c.dev(owk), wbytes, c.stream());
+    const orbm_covis_graph g = {c.dev(ock), c.dev(ocw), c.dev(onc), c.dev(ook),
+                                c.dev(oow), c.dev(ono), c.dev(opa), c.dev(ofi)};
+    rc = orbm_update_connections_device(&g, nkf, ccap, c.dev(ocn), c.dev(okm), cap, kf_rank ? c.dev(okr) : nullptr,
+                                        c.dev(opt), c.dev(oop), c.dev(oob), nmp, c.dev(otg), ntargets, th, root,
+                                        c.dev(ost), c.dev(owk), wbytes, c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(ock, graph->conn_kf, sizeof(int) * R);
-    c.fetch(ocw, graph->conn_w, sizeof(int) * R);
-    c.fetch(onc, graph->nconn, sizeof(int) * K);
-    c.fetch(ook, graph->ord_kf, sizeof(int) * R);
-    c.fetch(oow, graph->ord_w, sizeof(int) * R);
-    c.fetch(ono, graph->nord, sizeof(int) * K);
-    c.fetch(opa, graph->parent, sizeof(int) * K);
-    c.fetch(ofi, graph->first, K);
-    c.fetch(ost, status, sizeof(int) * (size_t)ntargets);
     return c.finish();
 }
 

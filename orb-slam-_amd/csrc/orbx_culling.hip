@@ -479,41 +479,27 @@ orbx_status orbm_map_point_culling(int device, const int* recent, int nrecent, i
         return ORBX_EINVAL;
     const size_t K = (size_t)nkf, M = (size_t)nmp, R = (size_t)nrecent, E = (size_t)obs_ptr[nmp];
     HostCall c(device);
-    // an empty table still gets a block (never read), so that every device pointer is a valid one
-    auto in = [&c](const void* src, size_t bytes) { return bytes ? c.in(src, bytes) : c.in(nullptr, 64); };
-    const size_t orc = in(recent, sizeof(int) * R);
-    const size_t ocn = c.in(counts, sizeof(int) * K);
-    const size_t okm = c.in(kf_mp, sizeof(int) * K * (size_t)cap);
-    const size_t opt = in(pts, sizeof(orbm_map_point) * M);
-    const size_t oop = c.in(obs_ptr, sizeof(int) * (M + 1));
-    const size_t oob = in(obs, sizeof(orbm_observation) * E);
-    const size_t oer = in(obs_erased, E);
-    const size_t ono = in(nobs, sizeof(int) * M);
-    const size_t ofo = in(found, sizeof(int) * M);
-    const size_t ovi = in(visible, sizeof(int) * M);
-    const size_t ofk = in(first_kfid, sizeof(int) * M);
+    const auto orc = c.in(recent, R);
+    const auto ocn = c.in(counts, K);
+    const auto okm = c.inout(kf_mp, K * (size_t)cap);
+    const auto opt = c.inout(pts, M);
+    const auto oop = c.in(obs_ptr, M + 1);
+    const auto oob = c.in(obs, E);
+    const auto oer = c.inout(obs_erased, E);
+    const auto ono = c.in(nobs, M);
+    const auto ofo = c.in(found, M);
+    const auto ovi = c.in(visible, M);
+    const auto ofk = c.in(first_kfid, M);
     // the outputs go up as well: what the call does not write keeps its bits
-    const size_t ove = in(verdict, sizeof(int) * R);
-    const size_t oro = in(recent_out, sizeof(int) * R);
-    const size_t onr = c.in(nrecent_out, sizeof(int));
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const auto ove = c.inout(verdict, R);
+    const auto oro = c.inout(recent_out, R);
+    const auto onr = c.inout(nrecent_out, 1);
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
-    rc = orbm_map_point_culling_device(c.dev_as<const int>(orc), nrecent, cur_kfid, th_obs, c.dev_as<const int>(ocn),
-                                       c.dev_as<int>(okm), nkf, cap, c.dev_as<orbm_map_point>(opt),
-                                       c.dev_as<const int>(oop), c.dev_as<const orbm_observation>(oob), c.dev(oer),
-                                       nmp, c.dev_as<const int>(ono), c.dev_as<const int>(ofo),
-                                       c.dev_as<const int>(ovi), c.dev_as<const int>(ofk), c.dev_as<int>(ove),
-                                       c.dev_as<int>(oro), c.dev_as<int>(onr), c.stream());
+    rc = orbm_map_point_culling_device(c.dev(orc), nrecent, cur_kfid, th_obs, c.dev(ocn), c.dev(okm), nkf, cap,
+                                       c.dev(opt), c.dev(oop), c.dev(oob), c.dev(oer), nmp, c.dev(ono), c.dev(ofo),
+                                       c.dev(ovi), c.dev(ofk), c.dev(ove), c.dev(oro), c.dev(onr), c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(okm, kf_mp, sizeof(int) * K * (size_t)cap);
-    if (M) c.fetch(opt, pts, sizeof(orbm_map_point) * M);
-    if (E) c.fetch(oer, obs_erased, E);
-    if (R) {
-        c.fetch(ove, verdict, sizeof(int) * R);
-        c.fetch(oro, recent_out, sizeof(int) * R);
-    }
-    c.fetch(onr, nrecent_out, sizeof(int));
     return c.finish();
 }
 
@@ -533,58 +519,40 @@ orbx_status orbm_keyframe_culling(int device, const orbm_covis_graph* graph, int
     const size_t K = (size_t)nkf, M = (size_t)nmp, E = (size_t)obs_ptr[nmp], F = K * (size_t)cap, CC = (size_t)ccap;
     const size_t wbytes = orbm_culling_work_bytes(nmp);
     HostCall c(device);
-    auto in = [&c](const void* src, size_t bytes) { return bytes ? c.in(src, bytes) : c.in(nullptr, 64); };
-    const size_t ook = c.in(graph->ord_kf, sizeof(int) * K * CC);
-    const size_t ono = c.in(graph->nord, sizeof(int) * K);
-    const size_t ocn = c.in(counts, sizeof(int) * K);
-    const size_t okm = c.in(kf_mp, sizeof(int) * F);
-    const size_t okp = c.in(kps, sizeof(orbx_keypoint) * F);
-    const size_t our = in(uright, uright ? sizeof(float) * F : 0);
-    const size_t ode = in(depth, depth ? sizeof(float) * F : 0);
-    const size_t one = c.in(kf_noterase, K);
-    const size_t opt = in(pts, sizeof(orbm_map_point) * M);
-    const size_t oop = c.in(obs_ptr, sizeof(int) * (M + 1));
-    const size_t oob = in(obs, sizeof(orbm_observation) * E);
-    const size_t oer = in(obs_erased, E);
-    const size_t orf = in(ref, sizeof(orbm_observation) * M);
-    const size_t onb = in(nobs, sizeof(int) * M);
-    const size_t ove = c.in(verdict, sizeof(int) * CC);
-    const size_t onm = c.in(nmps, sizeof(int) * CC);
-    const size_t onr = c.in(nred, sizeof(int) * CC);
-    const size_t ocu = c.in(culled, sizeof(int) * CC);
-    const size_t onc = c.in(nculled, sizeof(int));
-    const size_t ocd = c.in(ncand, sizeof(int));
-    const size_t owk = c.out(wbytes);
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const auto ook = c.in(graph->ord_kf, K * CC);
+    const auto ono = c.in(graph->nord, K);
+    const auto ocn = c.in(counts, K);
+    const auto okm = c.inout(kf_mp, F);
+    const auto okp = c.in(kps, F);
+    const auto our = c.in(uright, uright ? F : 0);
+    const auto ode = c.in(depth, depth ? F : 0);
+    const auto one = c.in(kf_noterase, K);
+    const auto opt = c.inout(pts, M);
+    const auto oop = c.in(obs_ptr, M + 1);
+    const auto oob = c.in(obs, E);
+    const auto orf = c.inout(ref, M);
+    const auto onb = c.inout(nobs, M);
+    const auto oer = c.inout(obs_erased, E);
+    const auto ove = c.inout(verdict, CC);
+    const auto onm = c.inout(nmps, CC);
+    const auto onr = c.inout(nred, CC);
+    const auto ocu = c.inout(culled, CC);
+    const auto onc = c.inout(nculled, 1);
+    const auto ocd = c.inout(ncand, 1);
+    const auto owk = c.out<uint8_t>(wbytes);
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
     if (hipMemsetAsync(c.dev(owk), 0, wbytes, c.stream()) != hipSuccess) return ORBX_EDEVICE;
     orbm_covis_graph g;
     std::memset(&g, 0, sizeof g);
-    g.ord_kf = c.dev_as<int32_t>(ook);
-    g.nord = c.dev_as<int32_t>(ono);
-    rc = orbm_keyframe_culling_device(&g, nkf, ccap, t, root, c.dev_as<const int>(ocn), c.dev_as<int>(okm), cap,
-                                      c.dev_as<const orbx_keypoint>(okp),
-                                      uright ? c.dev_as<const float>(our) : nullptr, c.dev_as<const float>(ode),
-                                      th_depth, stereo, nlevels, c.dev(one), c.dev_as<orbm_map_point>(opt),
-                                      c.dev_as<const int>(oop), c.dev_as<const orbm_observation>(oob), c.dev(oer),
-                                      c.dev_as<orbm_observation>(orf), c.dev_as<int>(onb), nmp, c.dev_as<int>(ove),
-                                      c.dev_as<int>(onm), c.dev_as<int>(onr), c.dev_as<int>(ocu), c.dev_as<int>(onc),
-                                      c.dev_as<int>(ocd), c.dev(owk), wbytes, c.stream());
+    g.ord_kf = c.dev(ook);
+    g.nord = c.dev(ono);
+    rc = orbm_keyframe_culling_device(&g, nkf, ccap, t, root, c.dev(ocn), c.dev(okm), cap, c.dev(okp),
+                                      uright ? c.dev(our) : nullptr, c.dev(ode), th_depth, stereo, nlevels, c.dev(one),
+                                      c.dev(opt), c.dev(oop), c.dev(oob), c.dev(oer), c.dev(orf), c.dev(onb), nmp,
+                                      c.dev(ove), c.dev(onm), c.dev(onr), c.dev(ocu), c.dev(onc), c.dev(ocd),
+                                      c.dev(owk), wbytes, c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(okm, kf_mp, sizeof(int) * F);
-    if (M) {
-        c.fetch(opt, pts, sizeof(orbm_map_point) * M);
-        c.fetch(orf, ref, sizeof(orbm_observation) * M);
-        c.fetch(onb, nobs, sizeof(int) * M);
-    }
-    if (E) c.fetch(oer, obs_erased, E);
-    c.fetch(ove, verdict, sizeof(int) * CC);
-    c.fetch(onm, nmps, sizeof(int) * CC);
-    c.fetch(onr, nred, sizeof(int) * CC);
-    c.fetch(ocu, culled, sizeof(int) * CC);
-    c.fetch(onc, nculled, sizeof(int));
-    c.fetch(ocd, ncand, sizeof(int));
     return c.finish();
 }
 
@@ -599,23 +567,17 @@ orbx_status orbm_compact_observations(int device, const int* obs_ptr, const orbm
         if (obs_ptr[m + 1] - obs_ptr[m] > ORBM_MAX_OBSERVATIONS) return ORBX_EINVAL;
     const size_t M = (size_t)nmp, E = (size_t)obs_ptr[nmp];
     HostCall c(device);
-    auto in = [&c](const void* src, size_t bytes) { return bytes ? c.in(src, bytes) : c.in(nullptr, 64); };
-    const size_t oop = c.in(obs_ptr, sizeof(int) * (M + 1));
-    const size_t oob = in(obs, sizeof(orbm_observation) * E);
-    const size_t oer = in(obs_erased, E);
-    const size_t opo = c.in(obs_ptr_out, sizeof(int) * (M + 1));
-    const size_t ooo = in(obs_out, sizeof(orbm_observation) * E);
-    const size_t ost = c.in(status, sizeof(int));
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const auto oop = c.in(obs_ptr, M + 1);
+    const auto oob = c.in(obs, E);
+    const auto oer = c.in(obs_erased, E);
+    const auto opo = c.inout(obs_ptr_out, M + 1);
+    const auto ooo = c.inout(obs_out, E);
+    const auto ost = c.inout(status, 1);
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
-    rc = orbm_compact_observations_device(c.dev_as<const int>(oop), c.dev_as<const orbm_observation>(oob), c.dev(oer),
-                                          nmp, c.dev_as<int>(opo), c.dev_as<orbm_observation>(ooo),
-                                          c.dev_as<int>(ost), c.stream());
+    rc = orbm_compact_observations_device(c.dev(oop), c.dev(oob), c.dev(oer), nmp, c.dev(opo), c.dev(ooo), c.dev(ost),
+                                          c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(opo, obs_ptr_out, sizeof(int) * (M + 1));
-    if (E) c.fetch(ooo, obs_out, sizeof(orbm_observation) * E);
-    c.fetch(ost, status, sizeof(int));
     return c.finish();
 }
 

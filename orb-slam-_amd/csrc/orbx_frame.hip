@@ -212,21 +212,19 @@ orbx_status orbx_rgbd_stereo(int device, const orbx_keypoint* kps, const orbx_ke
         if (!(kps[i].x >= 0.0f && kps[i].x < (float)cols && kps[i].y >= 0.0f && kps[i].y < (float)rows))
             return ORBX_EINVAL;
     HostCall c(device);
-    const size_t ocn = c.in(&n, sizeof(int));
-    const size_t ok = c.in(kps, sizeof(orbx_keypoint) * (size_t)n);
-    const size_t oku = c.in(kps_un, sizeof(orbx_keypoint) * (size_t)n);
-    const size_t od = c.in(depth, depth_step * (size_t)rows);
-    const size_t oo = c.out(sizeof(float) * 2 * (size_t)n);
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const size_t N = (size_t)n;
+    const auto ocn = c.in(&n, 1);
+    const auto ok = c.in(kps, N);
+    const auto oku = c.in(kps_un, N);
+    const auto od = c.in(depth, depth_step / 4 * (size_t)rows);   // depth_step is a multiple of 4
+    const auto oo = c.out<float>(2 * N);                          // uright, depth_out
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
-    float* dout = c.dev_as<float>(oo);
-    rc = orbx_rgbd_stereo_batch_device(c.dev_as<const orbx_keypoint>(ok), c.dev_as<const orbx_keypoint>(oku),
-                                       c.dev_as<const int>(ocn), 1, n, c.dev_as<const float>(od), rows, cols,
-                                       depth_step, 0, bf, dout, dout + n, c.stream());
+    rc = orbx_rgbd_stereo_batch_device(c.dev(ok), c.dev(oku), c.dev(ocn), 1, n, c.dev(od), rows, cols, depth_step, 0,
+                                       bf, c.dev(oo), c.dev(oo, N), c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(oo, uright, sizeof(float) * (size_t)n);
-    c.fetch(oo + sizeof(float) * (size_t)n, depth_out, sizeof(float) * (size_t)n);
+    c.fetch(oo, uright, N);
+    c.fetch(oo, depth_out, N, N);
     return c.finish();
 }
 
@@ -255,20 +253,18 @@ orbx_status orbm_frustum(int device, const orbm_map_point* pts, int np, const fl
     if (np == 0) return ORBX_OK;
     if (!pts || !out) return ORBX_EINVAL;
     HostCall c(device);
-    const size_t ocn = c.in(&np, sizeof(int));
-    const size_t opo = c.in(pose, sizeof(float) * 12);
-    const size_t op = c.in(pts, sizeof(orbm_map_point) * (size_t)np);
-    const size_t on = c.out(sizeof(int));
-    const size_t oo = c.out(sizeof(orbm_proj_point) * (size_t)np);
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const auto ocn = c.in(&np, 1);
+    const auto opo = c.in(pose, 12);
+    const auto op = c.in(pts, (size_t)np);
+    const auto on = c.out<int>(1);
+    const auto oo = c.out<orbm_proj_point>((size_t)np);
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
-    rc = orbm_frustum_batch_device(c.dev_as<const orbm_map_point>(op), c.dev_as<const int>(ocn), 1, np,
-                                   c.dev_as<const float>(opo), params, viewing_cos_limit,
-                                   c.dev_as<orbm_proj_point>(oo), c.dev_as<int>(on), c.stream());
+    rc = orbm_frustum_batch_device(c.dev(op), c.dev(ocn), 1, np, c.dev(opo), params, viewing_cos_limit, c.dev(oo),
+                                   c.dev(on), c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(on, ninview, sizeof(int));
-    c.fetch(oo, out, sizeof(orbm_proj_point) * (size_t)np);
+    c.fetch(on, ninview, 1);
+    c.fetch(oo, out, (size_t)np);
     return c.finish();
 }
 

@@ -104,7 +104,7 @@ HostCall::~HostCall()
 
 hipStream_t HostCall::stream() const { return ctx_ ? ctx_->stream : nullptr; }
 
-size_t HostCall::in(const void* src, size_t bytes)
+size_t HostCall::put(const void* src, size_t bytes)
 {
     // inputs come first so that one copy uploads them all
     if (outs_started_) st_ = ORBX_EINVAL;
@@ -115,7 +115,7 @@ size_t HostCall::in(const void* src, size_t bytes)
     return off;
 }
 
-size_t HostCall::out(size_t bytes)
+size_t HostCall::reserve(size_t bytes)
 {
     outs_started_ = true;
     const size_t off = end_;
@@ -151,7 +151,7 @@ orbx_status HostCall::prepare()
     }
     for (Block& b : ins_) {
         if (b.src && b.bytes && b.off + b.bytes <= pin_) std::memcpy(ctx_->pinned + b.off, b.src, b.bytes);
-        if (!b.src && b.bytes && b.off + b.bytes > pin_) {   // filled through host(): its own staging copy
+        if (!b.src && b.bytes && b.off + b.bytes > pin_) {   // a staged block: its own host copy
             b.stage = (int)staged_.size();
             staged_.emplace_back(b.bytes);
         }
@@ -159,7 +159,7 @@ orbx_status HostCall::prepare()
     return ORBX_OK;
 }
 
-uint8_t* HostCall::host(size_t off)
+uint8_t* HostCall::staged_at(size_t off)
 {
     if (!ctx_ || st_ != ORBX_OK) return nullptr;
     for (const Block& b : ins_) {
@@ -170,7 +170,7 @@ uint8_t* HostCall::host(size_t off)
     return nullptr;
 }
 
-uint8_t* HostCall::dev(size_t off) const { return ctx_ ? ctx_->dbuf + off : nullptr; }
+uint8_t* HostCall::at(size_t off) const { return ctx_ ? ctx_->dbuf + off : nullptr; }
 
 orbx_status HostCall::upload()
 {
@@ -188,7 +188,7 @@ orbx_status HostCall::upload()
     return ORBX_OK;
 }
 
-void HostCall::fetch(size_t off, void* dst, size_t bytes)
+void HostCall::get(size_t off, void* dst, size_t bytes)
 {
     if (bytes && dst) fetches_.push_back({off, bytes, dst});
 }

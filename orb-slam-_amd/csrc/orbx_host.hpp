@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "orbx_pack.hpp"
 
 namespace orbx {
 
@@ -45,18 +46,32 @@ private:
 
 struct HostCtx;
 
+// A block of a host call's layout: n elements of T at a byte offset both buffers share.
+template <class T>
+struct Blk {
+    size_t off = 0, n = 0;
+};
+// An input block the wrapper fills itself, through HostCall::host().
+template <class T>
+struct Staged : Blk<T> {};
+
 // One synchronous host call.  Usage:
 //   HostCall c(device);                      // check a context out of the pool
-//   size_t a = c.in(src, bytes) ...;         // input blocks (copied at prepare())
-//   size_t o = c.out(bytes) ...;             // device-only blocks (outputs, scratch), after the inputs
-//   c.prepare();                             // size the buffers, fill the pinned inputs
-//   c.host(a) ...                            // optional: fill or patch an input block (src NULL or not)
-//   c.upload();                              // H2D of the input prefix on the call's stream
-//   launch ...(c.dev(o), c.stream())
-//   c.fetch(o, dst, bytes) ...; c.finish();  // D2H, stream sync, copy out
+//   auto a = c.in(src, n);                   // input block of n elements, copied from src
+//   auto x = c.inout(ptr, n);                // input block that is also copied back to ptr by finish()
+//   auto s = c.stage<T>(n);                  // input block the wrapper fills through host(s)
+//   auto o = c.out<T>(n);                    // device-only blocks (outputs, scratch), after the inputs
+//   c.begin();                               // size the buffers, fill the pinned inputs, H2D on the call's stream;
+//                                            //   or prepare(), fill host(s) / patch in dev() pointers, upload()
+//   launch ...(c.dev(a), c.dev(o, first), c.stream())
+//   c.fetch(o, dst, n, first) ...; c.finish();   // D2H, stream sync, copy out
+// An array states its type and length once, where its block is declared.  A block of no elements still
+// reserves one slot that is never copied, so that every device pointer is a valid one.  Copies back are
+// only queued (inout() blocks first, in the order declared, then the fetch() calls): a wrapper that returns
+// before finish() writes nothing to the caller's arrays.
 // Blocks are 64-byte aligned.  Blocks inside the pinned window go through pinned memory; larger
-// layouts copy their tail blocks directly from / to the caller's memory, or, for an input block
-// without a source (filled through host()), from a host-side staging copy of its own.
+// layouts copy their tail blocks directly from / to the caller's memory, or, for a staged block, from a
+// host-side copy of its own.
 // A context's pinned buffer only grows; a replaced one is retired, not freed (hipHostFree waits for
 // the whole device, which would stall every other thread's stream).
 class HostCall {
@@ -69,15 +84,39 @@ public:
     orbx_status status() const { return st_; }
     hipStream_t stream() const;
 
-    size_t in(const void* src, size_t bytes);
-    size_t out(size_t bytes);
-    orbx_status prepare();
-    uint8_t* host(size_t off);         // staged copy of the input block at off (prepare() first)
-    orbx_status upload();
-    uint8_t* dev(size_t off) const;
+    // src NULL with n > 0: an array the device call never reads.  Reserved and uploaded with whatever the pinned
+    // buffer holds; past the pinned window prepare() cannot tell it from a stage() block and uploads zeros from a
+    // host copy of its own.  A wrapper that fills a block itself declares it with stage().
     template <class T>
-    T* dev_as(size_t off) const { return reinterpret_cast<T*>(dev(off)); }
-    void fetch(size_t off, void* dst, size_t bytes);
+    Blk<T> in(const T* src, size_t n) { return {put(n ? src : nullptr, bytes<T>(n)), n}; }
+    template <class T>
+    Blk<T> inout(T* ptr, size_t n)
+    {
+        const Blk<T> b = in(ptr, n);
+        fetch(b, ptr, n);
+        return b;
+    }
+    template <class T>
+    Staged<T> stage(size_t n) { return {{put(nullptr, bytes<T>(n)), n}}; }
+    template <class T>
+    Blk<T> out(size_t n) { return {reserve(bytes<T>(n)), n}; }
+
+    orbx_status prepare();
+    orbx_status upload();
+    orbx_status begin() { return prepare() == ORBX_OK ? upload() : st_; }
+    // the host copy of a staged block: never NULL after a successful prepare()
+    template <class T>
+    T* host(Staged<T> b) { return reinterpret_cast<T*>(staged_at(b.off)); }
+    // device address of element `first` of a block
+    template <class T>
+    T* dev(Blk<T> b, size_t first = 0) const { return reinterpret_cast<T*>(at(b.off)) + first; }
+    // queues the copy of elements [first, first + n) to dst (NULL: nothing)
+    template <class T>
+    void fetch(Blk<T> b, T* dst, size_t n, size_t first = 0)
+    {
+        if (first + n > b.n) st_ = ORBX_EINVAL;
+        else get(b.off + sizeof(T) * first, dst, sizeof(T) * n);
+    }
     orbx_status finish();
 
 private:
@@ -100,6 +139,14 @@ private:
     std::vector<std::vector<uint8_t>> staged_;
     size_t pin_ = 0;   // pinned window: blocks ending at or below it are staged through pinned memory
     bool queued_ = false;
+
+    template <class T>
+    static size_t bytes(size_t n) { return n ? sizeof(T) * n : 64; }
+    size_t put(const void* src, size_t bytes);
+    size_t reserve(size_t bytes);
+    uint8_t* staged_at(size_t off);
+    uint8_t* at(size_t off) const;
+    void get(size_t off, void* dst, size_t bytes);
 };
 
 }  // namespace orbx

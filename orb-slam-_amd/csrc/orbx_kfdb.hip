@@ -531,29 +531,27 @@ orbx_status detect_host(orbv_database* db, bool loop, const int32_t* q_word, con
     const size_t ns = (size_t)db->nslots;
     HostCall c(db->device);
     if (c.status() != ORBX_OK) return c.status();
-    const size_t oqn = c.in(&qn, sizeof(int));
-    const size_t oqw = c.in(q_word, (size_t)qn * sizeof(int32_t));
-    const size_t oqv = c.in(q_weight, (size_t)qn * sizeof(double));
-    const size_t oconn = c.in(loop ? connected : nullptr, loop && connected ? ns : 0);
-    const size_t ocov = c.in(covis, covis ? ns * orbx::kKfdbCovis * sizeof(int32_t) : 0);
-    const size_t onc = c.out(sizeof(int));
-    const size_t ocand = c.out(ns * sizeof(int));
-    const size_t owords = c.out(ns * sizeof(int));
-    const size_t oscores = c.out(ns * sizeof(float));
-    orbx_status st = c.prepare();
-    if (st == ORBX_OK) st = c.upload();
+    const auto oqn = c.in(&qn, 1);
+    const auto oqw = c.in(q_word, (size_t)qn);
+    const auto oqv = c.in(q_weight, (size_t)qn);
+    const auto oconn = c.in(connected, loop && connected ? ns : 0);
+    const auto ocov = c.in(covis, covis ? ns * orbx::kKfdbCovis : 0);
+    const auto onc = c.out<int>(1);
+    const auto ocand = c.out<int>(ns);
+    const auto owords = c.out<int>(ns);
+    const auto oscores = c.out<float>(ns);
+    orbx_status st = c.begin();
     if (st != ORBX_OK) return st;
-    st = query(db, loop, c.dev_as<int32_t>(oqw), c.dev_as<double>(oqv), c.dev_as<int>(oqn), qn,
-               loop && connected ? c.dev(oconn) : nullptr, covis ? c.dev_as<int32_t>(ocov) : nullptr, min_score,
-               c.dev_as<int>(ocand), c.dev_as<int>(onc), words ? c.dev_as<int>(owords) : nullptr,
-               scores ? c.dev_as<float>(oscores) : nullptr, c.stream());
+    st = query(db, loop, c.dev(oqw), c.dev(oqv), c.dev(oqn), qn, loop && connected ? c.dev(oconn) : nullptr,
+               covis ? c.dev(ocov) : nullptr, min_score, c.dev(ocand), c.dev(onc), words ? c.dev(owords) : nullptr,
+               scores ? c.dev(oscores) : nullptr, c.stream());
     if (st != ORBX_OK) return st;
     int nc = 0;
     std::vector<int> all(ns);
-    c.fetch(onc, &nc, sizeof(int));
-    c.fetch(ocand, all.data(), ns * sizeof(int));
-    c.fetch(owords, words, ns * sizeof(int));
-    c.fetch(oscores, scores, ns * sizeof(float));
+    c.fetch(onc, &nc, 1);
+    c.fetch(ocand, all.data(), ns);
+    c.fetch(owords, words, ns);
+    c.fetch(oscores, scores, ns);
     if ((st = c.finish()) != ORBX_OK) return st;
     db->ev_set = false;   // the call's stream has drained
     if (nc < 0 || (size_t)nc > ns) return ORBX_EDEVICE;
@@ -676,14 +674,13 @@ orbx_status orbv_db_add(orbv_database* db, const int32_t* bow_word, const double
     if (db->nslots >= ORBV_DB_MAX_KEYFRAMES) return ORBX_ENOSPC;
     HostCall c(db->device);
     if (c.status() != ORBX_OK) return c.status();
-    const size_t on = c.in(&n, sizeof(int));
-    const size_t ow = c.in(bow_word, (size_t)n * sizeof(int32_t));
-    const size_t ov = c.in(bow_weight, (size_t)n * sizeof(double));
-    orbx_status st = c.prepare();
-    if (st == ORBX_OK) st = c.upload();
+    const auto on = c.in(&n, 1);
+    const auto ow = c.in(bow_word, (size_t)n);
+    const auto ov = c.in(bow_weight, (size_t)n);
+    orbx_status st = c.begin();
     if (st != ORBX_OK) return st;
     const int cap = n > 0 ? n : 1;
-    st = append(db, c.dev_as<int32_t>(ow), c.dev_as<double>(ov), c.dev_as<int>(on), 1, cap, n, c.stream());
+    st = append(db, c.dev(ow), c.dev(ov), c.dev(on), 1, cap, n, c.stream());
     if (st != ORBX_OK) return st;
     if ((st = c.finish()) != ORBX_OK) return st;
     if (slot) *slot = db->nslots - 1;
@@ -773,22 +770,20 @@ orbx_status orbv_db_scores(orbv_database* db, const int32_t* q_word, const doubl
         if (slots[i] < 0 || slots[i] >= db->nslots) return ORBX_EINVAL;
     HostCall c(db->device);
     if (c.status() != ORBX_OK) return c.status();
-    const size_t oqn = c.in(&qn, sizeof(int));
-    const size_t oqw = c.in(q_word, (size_t)qn * sizeof(int32_t));
-    const size_t oqv = c.in(q_weight, (size_t)qn * sizeof(double));
-    const size_t osl = c.in(slots, (size_t)ns * sizeof(int));
-    const size_t osc = c.out((size_t)ns * sizeof(double));
-    orbx_status st = c.prepare();
-    if (st == ORBX_OK) st = c.upload();
+    const auto oqn = c.in(&qn, 1);
+    const auto oqw = c.in(q_word, (size_t)qn);
+    const auto oqv = c.in(q_weight, (size_t)qn);
+    const auto osl = c.in(slots, (size_t)ns);
+    const auto osc = c.out<double>((size_t)ns);
+    orbx_status st = c.begin();
     if (st != ORBX_OK) return st;
     follow(db, c.stream());
     const int nb = (ns + orbx::kKfdbScoreNT / 64 - 1) / (orbx::kKfdbScoreNT / 64);
     hipLaunchKernelGGL(orbx::k_kfdb_score, dim3(nb), dim3(orbx::kKfdbScoreNT), 0, c.stream(), db->d_ptr, db->d_n,
-                       db->d_live, db->d_word, db->d_weight, db->nslots, c.dev_as<int32_t>(oqw), c.dev_as<double>(oqv),
-                       c.dev_as<int>(oqn), qn, (const int*)nullptr, (const int*)nullptr, c.dev_as<int>(osl), ns,
-                       (float*)nullptr, c.dev_as<double>(osc));
+                       db->d_live, db->d_word, db->d_weight, db->nslots, c.dev(oqw), c.dev(oqv), c.dev(oqn), qn,
+                       (const int*)nullptr, (const int*)nullptr, c.dev(osl), ns, (float*)nullptr, c.dev(osc));
     if (hipGetLastError() != hipSuccess) return ORBX_EDEVICE;
-    c.fetch(osc, scores, (size_t)ns * sizeof(double));
+    c.fetch(osc, scores, (size_t)ns);
     if ((st = c.finish()) != ORBX_OK) return st;
     db->ev_set = false;
     return ORBX_OK;

@@ -598,61 +598,42 @@ orbx_status orbm_local_map(int device, const int* counts, const int* kf_mp, cons
     const size_t wbytes = orbm_local_map_work_bytes(nkf, nmp, 1, kfcap);
     const size_t K = (size_t)nkf, M = (size_t)nmp, N = (size_t)n;
     HostCall c(device);
-    // an empty table or list still gets a block (never read), so that every device pointer is a valid one
-    auto in = [&c](const void* src, size_t bytes) { return bytes ? c.in(src, bytes) : c.in(nullptr, 64); };
-    const int head[3] = {n, *nlocal_kf, *ref_kf};   // d_fcounts, d_nlocal_kf, d_ref_kf
-    const size_t oh = c.in(head, sizeof(head));
-    const size_t ocn = in(counts, sizeof(int) * K);
-    const size_t okm = in(kf_mp, sizeof(int) * K * (size_t)cap);
-    const size_t okb = in(kf_bad, K);
-    const size_t okr = in(kf_rank, kf_rank ? sizeof(int) * K : 0);
-    const size_t ocv = in(covis, sizeof(int) * 10 * K);
-    const size_t ocp = c.in(child_ptr, sizeof(int) * (K + 1));
-    const size_t och = in(child, sizeof(int) * (size_t)child_ptr[nkf]);
-    const size_t opa = in(parent, sizeof(int) * K);
-    const size_t opt = in(pts, sizeof(orbm_map_point) * M);
-    const size_t opd = in(pdesc, 32 * M);
-    const size_t oop = c.in(obs_ptr, sizeof(int) * (M + 1));
-    const size_t oob = in(obs, sizeof(orbm_observation) * (size_t)obs_ptr[nmp]);
-    const size_t ofm = in(frame_mp, sizeof(int) * N);
-    const size_t ofo = in(frame_outlier, frame_outlier ? sizeof(int) * N : 0);
+    const auto ofc = c.in(&n, 1);   // d_fcounts
+    const auto ocn = c.in(counts, K);
+    const auto okm = c.in(kf_mp, K * (size_t)cap);
+    const auto okb = c.in(kf_bad, K);
+    const auto okr = c.in(kf_rank, kf_rank ? K : 0);
+    const auto ocv = c.in(covis, 10 * K);
+    const auto ocp = c.in(child_ptr, K + 1);
+    const auto och = c.in(child, (size_t)child_ptr[nkf]);
+    const auto opa = c.in(parent, K);
+    const auto opt = c.in(pts, M);
+    const auto opd = c.in(pdesc, 32 * M);
+    const auto oop = c.in(obs_ptr, M + 1);
+    const auto oob = c.in(obs, (size_t)obs_ptr[nmp]);
+    const auto ofo = c.in(frame_outlier, frame_outlier ? N : 0);
     // outputs go up as well: what the call does not write keeps its bits
-    const size_t olk = c.in(local_kf, sizeof(int) * (size_t)kfcap);
-    const size_t olm = c.in(local_mp, sizeof(int) * (size_t)pcap);
-    const size_t oop2 = c.in(out_pts, sizeof(orbm_map_point) * (size_t)pcap);
-    const size_t ood = c.in(out_pdesc, 32 * (size_t)pcap);
-    const size_t ocl = in(claimed, N);
-    const int tail[2] = {*nlocal, *status};
-    const size_t otl = c.in(tail, sizeof(tail));
-    const size_t owk = c.out(wbytes);
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const auto ofm = c.inout(frame_mp, N);
+    const auto ocl = c.inout(claimed, N);
+    const auto olk = c.inout(local_kf, (size_t)kfcap);
+    const auto onk = c.inout(nlocal_kf, 1);
+    const auto ork = c.inout(ref_kf, 1);
+    const auto olm = c.inout(local_mp, (size_t)pcap);
+    const auto oop2 = c.inout(out_pts, (size_t)pcap);
+    const auto ood = c.inout(out_pdesc, 32 * (size_t)pcap);
+    const auto onl = c.inout(nlocal, 1);
+    const auto ost = c.inout(status, 1);
+    const auto owk = c.out<uint8_t>(wbytes);
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
     if (hipMemsetAsync(c.dev(owk), 0, wbytes, c.stream()) != hipSuccess) return ORBX_EDEVICE;
-    int* const dh = c.dev_as<int>(oh);
-    int* const dt = c.dev_as<int>(otl);
-    rc = orbm_local_map_device(c.dev_as<const int>(ocn), c.dev_as<const int>(okm), c.dev(okb),
-                               kf_rank && nkf > 0 ? c.dev_as<const int>(okr) : nullptr, c.dev_as<const int>(ocv),
-                               c.dev_as<const int>(ocp), c.dev_as<const int>(och), c.dev_as<const int>(opa), nkf, cap,
-                               c.dev_as<const orbm_map_point>(opt), c.dev(opd), c.dev_as<const int>(oop),
-                               c.dev_as<const orbm_observation>(oob), nmp, dh, c.dev_as<int>(ofm),
-                               frame_outlier && n > 0 ? c.dev_as<const int>(ofo) : nullptr, 1, fcap,
-                               c.dev_as<int>(olk), dh + 1, kfcap, dh + 2, c.dev_as<int>(olm), dt,
-                               c.dev_as<orbm_map_point>(oop2), c.dev(ood), pcap, c.dev(ocl), dt + 1, c.dev(owk),
-                               wbytes, c.stream());
+    rc = orbm_local_map_device(c.dev(ocn), c.dev(okm), c.dev(okb), kf_rank && nkf > 0 ? c.dev(okr) : nullptr,
+                               c.dev(ocv), c.dev(ocp), c.dev(och), c.dev(opa), nkf, cap, c.dev(opt), c.dev(opd),
+                               c.dev(oop), c.dev(oob), nmp, c.dev(ofc), c.dev(ofm),
+                               frame_outlier && n > 0 ? c.dev(ofo) : nullptr, 1, fcap, c.dev(olk), c.dev(onk), kfcap,
+                               c.dev(ork), c.dev(olm), c.dev(onl), c.dev(oop2), c.dev(ood), pcap, c.dev(ocl),
+                               c.dev(ost), c.dev(owk), wbytes, c.stream());
     if (rc != ORBX_OK) return rc;
-    if (n > 0) {
-        c.fetch(ofm, frame_mp, sizeof(int) * N);
-        c.fetch(ocl, claimed, N);
-    }
-    c.fetch(olk, local_kf, sizeof(int) * (size_t)kfcap);
-    c.fetch(oh + sizeof(int), nlocal_kf, sizeof(int));
-    c.fetch(oh + 2 * sizeof(int), ref_kf, sizeof(int));
-    c.fetch(olm, local_mp, sizeof(int) * (size_t)pcap);
-    c.fetch(oop2, out_pts, sizeof(orbm_map_point) * (size_t)pcap);
-    c.fetch(ood, out_pdesc, 32 * (size_t)pcap);
-    c.fetch(otl, nlocal, sizeof(int));
-    c.fetch(otl + sizeof(int), status, sizeof(int));
     return c.finish();
 }
 

@@ -255,31 +255,25 @@ orbx_status orbm_refresh_map_points(int device, int what, const orbx_keypoint* k
     if (max_obs > ORBM_MAX_OBSERVATIONS || (obs_ptr[np] > 0 && !obs)) return ORBX_EINVAL;
     const size_t nk = (size_t)nkf * (size_t)cap, no = (size_t)obs_ptr[np];
     HostCall c(device);
-    // an empty table or list still gets a block (never read), so that every device pointer is a valid one
-    auto in = [&c](const void* src, size_t bytes) { return bytes ? c.in(src, bytes) : c.in(nullptr, 64); };
-    const size_t ok = in(kps, sizeof(orbx_keypoint) * nk);
-    const size_t od = in(desc, 32 * nk);
-    const size_t oc = in(counts, sizeof(int) * (size_t)nkf);
-    const size_t opo = in(pose, sizeof(float) * 12 * (size_t)nkf);
-    const size_t ob = in(kf_bad, (size_t)nkf);
-    const size_t oop = c.in(obs_ptr, sizeof(int) * ((size_t)np + 1));
-    const size_t oo = in(obs, sizeof(orbm_observation) * no);
-    const size_t orf = c.in(ref, sizeof(orbm_observation) * (size_t)np);
-    const size_t op = c.in(pts, sizeof(orbm_map_point) * (size_t)np);
-    const size_t opd = c.in(pdesc, 32 * (size_t)np);
-    const size_t obt = c.out(sizeof(int) * (size_t)np);
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
+    const size_t K = (size_t)nkf, P = (size_t)np;
+    const auto ok = c.in(kps, nk);
+    const auto od = c.in(desc, 32 * nk);
+    const auto oc = c.in(counts, K);
+    const auto opo = c.in(pose, 12 * K);
+    const auto ob = c.in(kf_bad, K);
+    const auto oop = c.in(obs_ptr, P + 1);
+    const auto oo = c.in(obs, no);
+    const auto orf = c.in(ref, P);
+    const auto op = c.inout(pts, P);
+    const auto opd = c.inout(pdesc, 32 * P);
+    const auto obt = c.out<int>(P);
+    orbx_status rc = c.begin();
     if (rc != ORBX_OK) return rc;
-    rc = orbm_refresh_map_points_device(what, c.dev_as<const orbx_keypoint>(ok), c.dev(od), c.dev_as<const int>(oc),
-                                        nkf, cap, c.dev_as<const float>(opo), c.dev(ob), c.dev_as<const int>(oop),
-                                        c.dev_as<const orbm_observation>(oo), c.dev_as<const orbm_observation>(orf),
-                                        np, max_obs, params, c.dev_as<orbm_map_point>(op), c.dev(opd),
-                                        c.dev_as<int>(obt), c.stream());
+    rc = orbm_refresh_map_points_device(what, c.dev(ok), c.dev(od), c.dev(oc), nkf, cap, c.dev(opo), c.dev(ob),
+                                        c.dev(oop), c.dev(oo), c.dev(orf), np, max_obs, params, c.dev(op), c.dev(opd),
+                                        c.dev(obt), c.stream());
     if (rc != ORBX_OK) return rc;
-    c.fetch(op, pts, sizeof(orbm_map_point) * (size_t)np);
-    c.fetch(opd, pdesc, 32 * (size_t)np);
-    c.fetch(obt, best, sizeof(int) * (size_t)np);
+    c.fetch(obt, best, P);
     return c.finish();
 }
 

@@ -847,40 +847,38 @@ orbx_status orbm_pose_optimization(int device, const orbx_keypoint* kps, const f
         !po_args_ok(kps, uright, &n, 1, n > 0 ? n : 1, frame_mp, pts, nmp, pose_in, 12, params, flags, pose_out,
                     outlier, frame_outlier, ninliers, nmatches_map, trace, status))
         return ORBX_EINVAL;
-    const int cap = n > 0 ? n : 1;
-    HostCall c(device);
-    const size_t ocn = c.in(&n, sizeof(int));
-    const size_t opo = c.in(pose_in, sizeof(float) * 12);
-    const size_t ok = c.in(n ? kps : nullptr, sizeof(orbx_keypoint) * (size_t)cap);
-    const size_t our = c.in(n ? uright : nullptr, sizeof(float) * (size_t)cap);
-    const size_t omp = c.in(n ? frame_mp : nullptr, sizeof(int) * (size_t)cap);
-    const size_t oout = c.in(n ? outlier : nullptr, (size_t)cap);
-    const size_t op = c.in(nmp ? pts : nullptr, sizeof(orbm_map_point) * (size_t)(nmp > 0 ? nmp : 1));
-    const size_t ores = c.out(sizeof(int) * 3 + sizeof(float) * 12 + sizeof(orbm_pose_opt_trace));
-    const size_t ofo = c.out(sizeof(int) * (size_t)cap);
-    orbx_status rc = c.prepare();
-    if (rc == ORBX_OK) rc = c.upload();
-    if (rc != ORBX_OK) return rc;
-    int* dres = c.dev_as<int>(ores);   // status, ninliers, nmatches_map, pose_out[12], trace
-    float* dpose = reinterpret_cast<float*>(dres + 3);
-    orbm_pose_opt_trace* dtr = reinterpret_cast<orbm_pose_opt_trace*>(dpose + 12);
-    rc = orbm_pose_optimization_device(c.dev_as<const orbx_keypoint>(ok), c.dev_as<const float>(our),
-                                       c.dev_as<const int>(ocn), 1, cap, c.dev_as<int>(omp),
-                                       c.dev_as<const orbm_map_point>(op), nmp, c.dev_as<const float>(opo), 12, params,
-                                       flags, dpose, c.dev_as<uint8_t>(oout), c.dev_as<int>(ofo), dres + 1, dres + 2,
-                                       dtr, dres, c.stream());
-    if (rc != ORBX_OK) return rc;
-    struct {
+    // The per-feature blocks are sized by cap, not by in()'s own empty-block rule: the device call takes cap as
+    // its frame stride (which must be > 0) and the results are fetched cap elements at a time, so an empty frame
+    // is one element with no source, never read.
+    const size_t cap = n > 0 ? (size_t)n : 1;
+    struct Res {
         int status, ninliers, nmatches_map;
         float pose[12];
         orbm_pose_opt_trace tr;
     } res;
-    c.fetch(ores, &res, sizeof(res));
-    std::vector<int> mp_new((size_t)cap), fo_new((size_t)cap);
-    std::vector<uint8_t> out_new((size_t)cap);
-    c.fetch(omp, mp_new.data(), sizeof(int) * (size_t)cap);
-    c.fetch(oout, out_new.data(), (size_t)cap);
-    c.fetch(ofo, fo_new.data(), sizeof(int) * (size_t)cap);
+    HostCall c(device);
+    const auto ocn = c.in(&n, 1);
+    const auto opo = c.in(pose_in, 12);
+    const auto ok = c.in(n ? kps : nullptr, cap);
+    const auto our = c.in(n ? uright : nullptr, cap);
+    const auto omp = c.in(n ? frame_mp : nullptr, cap);
+    const auto oout = c.in(n ? outlier : nullptr, cap);
+    const auto op = c.in(pts, (size_t)nmp);
+    const auto ores = c.out<Res>(1);
+    const auto ofo = c.out<int>(cap);
+    orbx_status rc = c.begin();
+    if (rc != ORBX_OK) return rc;
+    Res* const d = c.dev(ores);
+    rc = orbm_pose_optimization_device(c.dev(ok), c.dev(our), c.dev(ocn), 1, (int)cap, c.dev(omp), c.dev(op), nmp,
+                                       c.dev(opo), 12, params, flags, d->pose, c.dev(oout), c.dev(ofo), &d->ninliers,
+                                       &d->nmatches_map, &d->tr, &d->status, c.stream());
+    if (rc != ORBX_OK) return rc;
+    c.fetch(ores, &res, 1);
+    std::vector<int> mp_new(cap), fo_new(cap);
+    std::vector<uint8_t> out_new(cap);
+    c.fetch(omp, mp_new.data(), cap);
+    c.fetch(oout, out_new.data(), cap);
+    c.fetch(ofo, fo_new.data(), cap);
     rc = c.finish();
     if (rc != ORBX_OK) return rc;
     *status = res.status;

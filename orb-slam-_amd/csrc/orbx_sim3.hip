@@ -874,78 +874,54 @@ orbx_status orbm_sim3_solve(int device, const orbx_keypoint* kps1, const int* kf
     s3_fill_maxits(&one, probability, min_inliers, max_iterations);
     const int cap = one.cap, nobs = one.nobs;
     const S3Layout L = s3_layout(1, cap, nit);
-    HostCall c(device);
-    const size_t okp = c.in(nullptr, sizeof(orbx_keypoint) * (size_t)2 * cap);
-    const size_t omp = c.in(nullptr, sizeof(int) * (size_t)2 * cap);
-    const size_t om12 = c.in(nullptr, sizeof(int) * (size_t)cap);
-    const size_t ohd = c.in(nullptr, sizeof(int) * 8 + sizeof(float) * 24);   // counts, pair, rand_off, state; pose
-    const size_t omx = c.in(one.maxits.data(), sizeof(int) * ((size_t)cap + 1));
-    const size_t ord = c.in(rand, sizeof(int) * (size_t)3 * nit);
-    const size_t opt = c.in(nmp ? pts : nullptr, sizeof(orbm_map_point) * (size_t)(nmp > 0 ? nmp : 1));
-    const size_t oop = c.in(nmp ? obs_ptr : nullptr, sizeof(int) * ((size_t)nmp + 1));
-    const size_t oob = c.in(nobs ? obs : nullptr, sizeof(orbm_observation) * (size_t)(nobs > 0 ? nobs : 1));
-    const size_t oer = c.in(nobs && obs_erased ? obs_erased : nullptr, (size_t)(nobs > 0 ? nobs : 1));
-    const size_t ores = c.out(sizeof(int) * 8 + sizeof(float) * 16);   // n, status, ninl, nomore, used, 2 scratch; sim3
-    const size_t oin = c.out((size_t)cap);
-    const size_t oal = c.out((size_t)cap);
-    const size_t owk = c.out(L.total);
-    orbx_status rc = c.prepare();
-    if (rc != ORBX_OK) return rc;
-    {
-        orbx_keypoint* k = reinterpret_cast<orbx_keypoint*>(c.host(okp));
-        int* mp = reinterpret_cast<int*>(c.host(omp));
-        int* m = reinterpret_cast<int*>(c.host(om12));
-        std::memset(k, 0, sizeof(orbx_keypoint) * (size_t)2 * cap);
-        for (int i = 0; i < 2 * cap; ++i) mp[i] = -1;
-        for (int i = 0; i < cap; ++i) m[i] = -1;
-        if (n1) {
-            std::memcpy(k, kps1, sizeof(orbx_keypoint) * (size_t)n1);
-            std::memcpy(mp, kf_mp1, sizeof(int) * (size_t)n1);
-            std::memcpy(m, match12, sizeof(int) * (size_t)n1);
-        }
-        if (n2) {
-            std::memcpy(k + cap, kps2, sizeof(orbx_keypoint) * (size_t)n2);
-            std::memcpy(mp + cap, kf_mp2, sizeof(int) * (size_t)n2);
-        }
-        int* hd = reinterpret_cast<int*>(c.host(ohd));
-        hd[0] = n1;
-        hd[1] = n2;
-        hd[2] = 0;   // pair_a
-        hd[3] = 1;   // pair_b
-        hd[4] = 0;   // rand_off
-        hd[5] = *iterations;
-        hd[6] = *best_inliers;
-        hd[7] = 0;
-        std::memcpy(hd + 8, T1w, sizeof(float) * 12);
-        std::memcpy(reinterpret_cast<float*>(hd + 8) + 12, T2w, sizeof(float) * 12);
-    }
-    rc = c.upload();
-    if (rc != ORBX_OK) return rc;
-    int* hd = c.dev_as<int>(ohd);
-    int* res = c.dev_as<int>(ores);
-    float* dsim3 = reinterpret_cast<float*>(res + 8);
-    // the constructor's own zero state goes to the two scratch words; iterate starts from the caller's state
-    rc = orbm_sim3_setup_device(c.dev_as<const orbx_keypoint>(okp), hd, 2, cap, reinterpret_cast<const float*>(hd + 8),
-                                c.dev_as<const int>(omp), nmp ? c.dev_as<const orbm_map_point>(opt) : nullptr, nmp,
-                                nmp ? c.dev_as<const int>(oop) : nullptr, c.dev_as<const orbm_observation>(oob),
-                                nobs && obs_erased ? c.dev_as<const uint8_t>(oer) : nullptr, hd + 2, hd + 3, 1,
-                                c.dev_as<const int>(om12), cap, params, c.dev_as<const int>(omx), c.dev(owk), L.total,
-                                res, res + 5, res + 6, res + 1, c.stream());
-    if (rc != ORBX_OK) return rc;
-    rc = orbm_sim3_iterate_device(c.dev(owk), L.total, 1, cap, params, fix_scale, min_inliers, nit,
-                                  c.dev_as<const int>(ord), hd + 4, hd + 5, hd + 6, dsim3, c.dev_as<uint8_t>(oin),
-                                  c.dev_as<uint8_t>(oal), res + 2, res + 3, res + 4, c.stream());
-    if (rc != ORBX_OK) return rc;
-    struct {
-        int n, status, ninliers, nomore, used, s0, s1, pad;
+    const size_t C = (size_t)cap, m1 = (size_t)n1, m2 = (size_t)n2;
+    const int head[8] = {n1, n2, 0, 1, 0, *iterations, *best_inliers, 0};   // counts, pair, rand_off, state, pad
+    struct Res {
+        int n, status, ninliers, nomore, used, s0, s1, pad;   // s0, s1: scratch
         float sim3[16];
     } r;
+    HostCall c(device);
+    const auto okp = c.stage<orbx_keypoint>(2 * C);
+    const auto omp = c.stage<int>(2 * C);
+    const auto om12 = c.stage<int>(C);
+    const auto ohd = c.in(head, 8);
+    const auto opo = c.stage<float>(24);
+    const auto omx = c.in(one.maxits.data(), C + 1);
+    const auto ord = c.in(rand, (size_t)3 * nit);
+    const auto opt = c.in(pts, (size_t)nmp);
+    const auto oop = c.in(nmp ? obs_ptr : nullptr, (size_t)nmp + 1);
+    const auto oob = c.in(obs, (size_t)nobs);
+    const auto oer = c.in(obs_erased, (size_t)nobs);
+    const auto ores = c.out<Res>(1);
+    const auto oin = c.out<uint8_t>(C);
+    const auto oal = c.out<uint8_t>(C);
+    const auto owk = c.out<uint8_t>(L.total);
+    orbx_status rc = c.prepare();
+    if (rc != ORBX_OK) return rc;
+    pack_pair(c.host(okp), C, kps1, m1, kps2, m2);
+    pack_pair(c.host(omp), C, kf_mp1, m1, kf_mp2, m2, 0xFF);
+    std::fill_n(std::copy_n(match12, m1, c.host(om12)), C - m1, -1);
+    pack_pair(c.host(opo), 12, T1w, 12, T2w, 12);
+    rc = c.upload();
+    if (rc != ORBX_OK) return rc;
+    Res* const d = c.dev(ores);
+    // the constructor's own zero state goes to the two scratch words; iterate starts from the caller's state
+    rc = orbm_sim3_setup_device(c.dev(okp), c.dev(ohd), 2, cap, c.dev(opo), c.dev(omp), nmp ? c.dev(opt) : nullptr,
+                                nmp, nmp ? c.dev(oop) : nullptr, c.dev(oob),
+                                nobs && obs_erased ? c.dev(oer) : nullptr, c.dev(ohd, 2), c.dev(ohd, 3), 1,
+                                c.dev(om12), cap, params, c.dev(omx), c.dev(owk), L.total, &d->n, &d->s0, &d->s1,
+                                &d->status, c.stream());
+    if (rc != ORBX_OK) return rc;
+    rc = orbm_sim3_iterate_device(c.dev(owk), L.total, 1, cap, params, fix_scale, min_inliers, nit, c.dev(ord),
+                                  c.dev(ohd, 4), c.dev(ohd, 5), c.dev(ohd, 6), d->sim3, c.dev(oin), c.dev(oal),
+                                  &d->ninliers, &d->nomore, &d->used, c.stream());
+    if (rc != ORBX_OK) return rc;
     int state[2];
-    std::vector<uint8_t> in12((size_t)cap), al2((size_t)cap);
-    c.fetch(ores, &r, sizeof(r));
-    c.fetch(ohd + sizeof(int) * 5, state, sizeof(state));
-    c.fetch(oin, in12.data(), (size_t)cap);
-    c.fetch(oal, al2.data(), (size_t)cap);
+    std::vector<uint8_t> in12(C), al2(C);
+    c.fetch(ores, &r, 1);
+    c.fetch(ohd, state, 2, 5);
+    c.fetch(oin, in12.data(), C);
+    c.fetch(oal, al2.data(), C);
     rc = c.finish();
     if (rc != ORBX_OK) return rc;
     *status = r.status;

@@ -440,59 +440,46 @@ orbx_status orbm_triangulate(int device, const orbx_keypoint* kps1, const orbx_k
     std::memcpy(poses, T1w, sizeof(float) * 12);
     std::memcpy(poses + 12, T2w, sizeof(float) * 12);
     HostCall hc(device);
-    const size_t oh = hc.in(head, sizeof(head));
-    const size_t og = hc.in(poses, sizeof(poses));
-    const size_t ok = hc.in(nullptr, sizeof(orbx_keypoint) * 2 * c);
-    const size_t okr = hc.in(nullptr, sizeof(orbx_keypoint) * 2 * c);
-    const size_t ou = hc.in(nullptr, sizeof(float) * 2 * c);
-    const size_t odp = hc.in(nullptr, sizeof(float) * 2 * c);
-    const size_t om = hc.in(match, sizeof(int) * (size_t)n1);
-    const size_t omk = hc.in(nullptr, 2 * c);
-    const size_t ox = hc.in(x3d, sizeof(float) * 3 * (size_t)n1);   // entries of no created point keep their bits
-    const size_t os = hc.out(sizeof(int) * (c + 1));                // status[cap], nnew
-    const size_t op = hc.out(sizeof(orbm_map_point) * c);
-    const size_t oo = hc.out(sizeof(orbm_observation) * 3 * c);     // new_obs[2 * cap], new_ref[cap]
-    const size_t oi = hc.out(sizeof(int) * c);
+    const size_t m1 = (size_t)n1, m2 = (size_t)n2;
+    const auto oh = hc.in(head, 4);
+    const auto og = hc.in(poses, 24);
+    const auto ok = hc.stage<orbx_keypoint>(2 * c);
+    const auto okr = hc.stage<orbx_keypoint>(2 * c);
+    const auto ou = hc.stage<float>(2 * c);
+    const auto odp = hc.stage<float>(2 * c);
+    const auto om = hc.in(match, m1);
+    const auto omk = hc.stage<uint8_t>(2 * c);
+    const auto ox = hc.inout(x3d, 3 * m1);                  // entries of no created point keep their bits
+    const auto os = hc.out<int>(c + 1);                     // status[cap], nnew
+    const auto op = hc.out<orbm_map_point>(c);
+    const auto oo = hc.out<orbm_observation>(3 * c);        // new_obs[2 * cap], new_ref[cap]
+    const auto oi = hc.out<int>(c);
     orbx_status rc = hc.prepare();
     if (rc != ORBX_OK) return rc;
-    auto pack = [&](size_t off, const void* a, const void* b, size_t elem) {
-        uint8_t* h = hc.host(off);
-        std::memset(h, 0, elem * 2 * c);
-        if (a) std::memcpy(h, a, elem * (size_t)n1);
-        if (b && n2 > 0) std::memcpy(h + elem * c, b, elem * (size_t)n2);
-    };
-    pack(ok, kps1, kps2, sizeof(orbx_keypoint));
-    pack(okr, kps1_raw, kps2_raw, sizeof(orbx_keypoint));
-    pack(ou, uright1, uright2, sizeof(float));
-    pack(odp, depth1, depth2, sizeof(float));
-    pack(omk, mark1, mark2, 1);
+    pack_pair(hc.host(ok), c, kps1, m1, kps2, m2);
+    pack_pair(hc.host(okr), c, kps1_raw, m1, kps2_raw, m2);
+    pack_pair(hc.host(ou), c, uright1, m1, uright2, m2);
+    pack_pair(hc.host(odp), c, depth1, m1, depth2, m2);
+    pack_pair(hc.host(omk), c, mark1, m1, mark2, m2);
     if ((rc = hc.upload()) != ORBX_OK) return rc;
-    const int* dh = hc.dev_as<const int>(oh);
-    int* ds = hc.dev_as<int>(os);
-    orbm_observation* dobs = hc.dev_as<orbm_observation>(oo);
-    rc = orbm_triangulate_device(hc.dev_as<const orbx_keypoint>(ok),
-                                 kps1_raw ? hc.dev_as<const orbx_keypoint>(okr) : nullptr,
-                                 stereo ? hc.dev_as<const float>(ou) : nullptr,
-                                 stereo ? hc.dev_as<const float>(odp) : nullptr, dh, 2, cap,
-                                 hc.dev_as<const float>(og), nullptr, dh + 2, dh + 3, 1, hc.dev_as<const int>(om), cap,
-                                 params, hc.dev_as<float>(ox), ds, hc.dev_as<orbm_map_point>(op), dobs, dobs + 2 * c,
-                                 hc.dev_as<int>(oi), ds + c, mark1 ? hc.dev(omk) : nullptr, hc.stream());
+    rc = orbm_triangulate_device(hc.dev(ok), kps1_raw ? hc.dev(okr) : nullptr, stereo ? hc.dev(ou) : nullptr,
+                                 stereo ? hc.dev(odp) : nullptr, hc.dev(oh), 2, cap, hc.dev(og), nullptr,
+                                 hc.dev(oh, 2), hc.dev(oh, 3), 1, hc.dev(om), cap, params, hc.dev(ox), hc.dev(os),
+                                 hc.dev(op), hc.dev(oo), hc.dev(oo, 2 * c), hc.dev(oi), hc.dev(os, c),
+                                 mark1 ? hc.dev(omk) : nullptr, hc.stream());
     if (rc != ORBX_OK) return rc;
     // the compacted arrays are fetched whole: entries at and past *nnew hold whatever the device block held
-    hc.fetch(ox, x3d, sizeof(float) * 3 * (size_t)n1);
-    hc.fetch(os, status, sizeof(int) * (size_t)n1);
-    hc.fetch(os + sizeof(int) * c, nnew, sizeof(int));
-    if (mark1) {
-        hc.fetch(omk, mark1, (size_t)n1);
-        if (n2 > 0) hc.fetch(omk + c, mark2, (size_t)n2);
-    }
+    hc.fetch(os, status, m1);
+    hc.fetch(os, nnew, 1, c);
+    hc.fetch(omk, mark1, m1);
+    hc.fetch(omk, mark2, m2, c);
     // staged: only the first *nnew compacted entries are the call's
     std::vector<orbm_map_point> hp(c);
     std::vector<orbm_observation> ho(3 * c);
     std::vector<int> hi(c);
-    hc.fetch(op, hp.data(), sizeof(orbm_map_point) * c);
-    hc.fetch(oo, ho.data(), sizeof(orbm_observation) * 3 * c);
-    hc.fetch(oi, hi.data(), sizeof(int) * c);
+    hc.fetch(op, hp.data(), c);
+    hc.fetch(oo, ho.data(), 3 * c);
+    hc.fetch(oi, hi.data(), c);
     if ((rc = hc.finish()) != ORBX_OK) return rc;
     const size_t k = (size_t)std::max(0, std::min(*nnew, n1));
     std::memcpy(new_pts, hp.data(), sizeof(orbm_map_point) * k);

@@ -400,30 +400,28 @@ orbx_status orbv_transform(const orbx_vocabulary* v, const uint8_t* desc, int n,
     if (!desc || !bow_word || !bow_weight || !fv_node || !fv_idx) return ORBX_EINVAL;
     const size_t cap = (size_t)n;
     orbx::HostCall c(v->device);
-    const size_t ocnt = c.in(&n, sizeof(int));
-    const size_t odesc = c.in(desc, cap * 32);
-    const size_t ometa = c.out(2 * sizeof(int));   // bow_n, fv_nnodes
-    const size_t obw = c.out(cap * sizeof(double));
-    const size_t obwd = c.out(cap * sizeof(int32_t));
-    const size_t ofnode = c.out(cap * sizeof(int32_t));
-    const size_t ofptr = c.out((cap + 1) * sizeof(int32_t));
-    const size_t ofidx = c.out(cap * sizeof(int32_t));
-    orbx_status st = c.prepare();
-    if (st == ORBX_OK) st = c.upload();
+    const auto ocnt = c.in(&n, 1);
+    const auto odesc = c.in(desc, cap * 32);
+    const auto ometa = c.out<int>(2);   // bow_n, fv_nnodes
+    const auto obw = c.out<double>(cap);
+    const auto obwd = c.out<int32_t>(cap);
+    const auto ofnode = c.out<int32_t>(cap);
+    const auto ofptr = c.out<int32_t>(cap + 1);
+    const auto ofidx = c.out<int32_t>(cap);
+    orbx_status st = c.begin();
     if (st != ORBX_OK) return st;
-    int* meta = c.dev_as<int>(ometa);
-    st = orbv_transform_batch_device(v, c.dev(odesc), c.dev_as<const int>(ocnt), 1, n, levelsup,
-                                     c.dev_as<int32_t>(obwd), c.dev_as<double>(obw), meta, c.dev_as<int32_t>(ofnode),
-                                     c.dev_as<int32_t>(ofptr), c.dev_as<int32_t>(ofidx), meta + 1, c.stream());
+    st = orbv_transform_batch_device(v, c.dev(odesc), c.dev(ocnt), 1, n, levelsup, c.dev(obwd), c.dev(obw),
+                                     c.dev(ometa), c.dev(ofnode), c.dev(ofptr), c.dev(ofidx), c.dev(ometa, 1),
+                                     c.stream());
     if (st != ORBX_OK) return st;
     // every output has room for n entries: fetch them whole with the counts (one round trip)
     int m[2] = {0, 0};
-    c.fetch(ometa, m, sizeof(m));
-    c.fetch(obwd, bow_word, cap * sizeof(int32_t));
-    c.fetch(obw, bow_weight, cap * sizeof(double));
-    c.fetch(ofnode, fv_node, cap * sizeof(int32_t));
-    c.fetch(ofptr, fv_ptr, (cap + 1) * sizeof(int32_t));
-    c.fetch(ofidx, fv_idx, cap * sizeof(int32_t));
+    c.fetch(ometa, m, 2);
+    c.fetch(obwd, bow_word, cap);
+    c.fetch(obw, bow_weight, cap);
+    c.fetch(ofnode, fv_node, cap);
+    c.fetch(ofptr, fv_ptr, cap + 1);
+    c.fetch(ofidx, fv_idx, cap);
     if ((st = c.finish()) != ORBX_OK) return st;
     *bow_n = m[0];
     *fv_nnodes = m[1];

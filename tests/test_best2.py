@@ -67,6 +67,14 @@ def test_gpu_best2_csr(orbref, cuda, tie_mode):
         want = orbref.best2_csr(q, t, ptr, idx, bool(tie_mode))
         for a, b in zip(got, want):
             assert np.array_equal(a, b)
+    # no candidate at all, and no target: the host call's candidate and target tables are empty
+    q, t, _, idx = case(5, nq=70, nt=20)
+    none = np.zeros(71, np.int32)
+    for tt in (t, t[:0]):
+        got = orbx.best2_csr(q, tt, none, idx[:0], tie_mode)
+        for a, b in zip(got, orbref.best2_csr(q, t, none, idx[:0], bool(tie_mode))):
+            assert np.array_equal(a, b)
+    assert (got[0] == -1).all() and (got[1] == 256).all()
 
 
 @pytest.mark.gpu

@@ -386,3 +386,6 @@ def test_gpu_bow_large_nodes_and_edges(orbref, cuda):
     empty = (np.zeros(0, np.int32), np.zeros(1, np.int32), np.zeros(0, np.int32))
     n, mm = m.SearchByBoW_KF_KF((k1, d1, empty, mp), (k2, d2, fv_big, mp))
     assert n == 0 and np.all(mm == -1)
+    # a second view without keypoints: every table of that view is empty
+    n, mm = m.SearchByBoW_KF_KF((k1, d1, fv_big, mp), (k2[:0], d2[:0], empty, mp[:0]))
+    assert n == 0 and len(mm) == 400 and np.all(mm == -1)

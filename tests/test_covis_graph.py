@@ -871,3 +871,25 @@ def test_gpu_host_form_equals_device_form(cuda):
                             status=st)
     D, dst = run_both(cuda, T, G, targets, th, root=0)
     assert np.array_equal(st, dst) and st[-1] == INVALID and not graph_diff(H, G)
+
+
+@pytest.mark.gpu
+def test_gpu_host_form_empty_tables_and_no_rank(cuda):
+    """orbm_update_connections on host arrays without MapPoints and observations (nmp == 0), and over a small star
+    without d_kf_rank: each absent table is one slot the device call never reads.  The host form agrees with the
+    restatement (and, for the star, with the device form) on the statuses and on every graph field."""
+    import orbx
+    empty = table([[-1], [-1], [-1]], 0)
+    assert len(empty.pts) == 0 and len(empty.obs) == 0 and empty.rank is None
+    hub = star(9)
+    hub.rank = None
+    for T, targets in ((empty, [0, 2]), (hub, [0, 3, 8])):
+        G = blank_graph(T.nkf, 8)
+        H = copy_graph(G)
+        st = np.full(len(targets), SENT, np.int32)
+        orbx.update_connections(H, T.counts, T.kf_mp, T.pts, T.obs_ptr, T.obs, targets, th=1, status=st)
+        if T is empty:                                       # the device form takes no NULL table: restatement alone
+            want = py_update_connections(G, T, targets, 1, -1)
+        else:
+            _, want = run_both(cuda, T, G, targets, 1)
+        assert np.array_equal(st, want) and not graph_diff(H, G)

@@ -1088,6 +1088,21 @@ def test_gpu_compaction(cuda):
     assert status == ws == CONN_INVALID and np.array_equal(ptr, wp) and np.array_equal(obs, wo)
 
 
+@pytest.mark.gpu
+def test_gpu_host_forms_take_an_empty_table(cuda):
+    """No MapPoint, no observation, an empty recent list: every table of the host forms is a single slot that the
+    device call never reads.  Device form and host form against the restatement, as for every other scene."""
+    import orbx
+    E = CullTable(2, 4, 0)
+    E.set_lists([])
+    E.ord_kf[0, 0], E.nord[0] = 1, 1                         # one candidate, which holds no MapPoint
+    check_map_points(cuda, E, [], 10, 2)
+    _, _, want = check_keyframes(cuda, E)
+    assert want["ncand"] == 1 and want["nculled"] == 0
+    host = orbx.compact_observations(E.obs_ptr, E.obs, E.erased)
+    assert host["status"] == 0 and host["obs_ptr"].tolist() == [0] and len(host["obs"]) == 0
+
+
 def chain_scene():
     """The random culling scene with what the refresh, the connections and the local map read beside it."""
     import orbx

@@ -228,6 +228,11 @@ def test_host_edge_cases(orbref, cuda):
     n, m12 = m.SearchForInitialization((big, bd), (k, d, (640, 480)), got_prev, 100)
     want = orbref.search_for_initialization(big, bd, k, d, 640, 480, prev_xy=_xy(big))
     _check("host 5000 x 3", n, m12, got_prev, want)
+    # fewer keypoints in F1 than in F2: F1's slots past its count are padding
+    got_prev = _xy(k)
+    n, m12 = m.SearchForInitialization((k, d), (big[:40], bd[:40], (640, 480)), got_prev, 100)
+    want = orbref.search_for_initialization(k, d, big[:40], bd[:40], 640, 480, prev_xy=_xy(k))
+    _check("host 3 x 40", n, m12, got_prev, want)
     # past the int16 match vectors: EINVAL
     with pytest.raises(orbx.OrbxError) as e:
         huge = np.zeros(40000, orbx.KEYPOINT_DTYPE)

@@ -232,3 +232,21 @@ def test_growing_host_calls_do_not_wait_for_other_streams(orbref, cuda, where):
                 wi, w1, w2 = orbref.allpairs_top2(q[:200], t)
                 assert np.array_equal(out[0][:200], wi) and np.array_equal(out[1][:200], w1)
     assert not slow, "growing host calls waited for the %s kernel: %s" % (where, slow)
+
+
+def test_host_call_past_the_pinned_window(cuda):
+    """A layout larger than the 64 MiB pinned window (csrc/orbx_host.hip): its tail block, here the 5800 x 5800
+    uint16 distance matrix of orbm_allpairs (67.3 MB), is copied straight to the caller's memory instead of through
+    the pinned buffer.  Every 19th row and the last one (307 rows) against numpy popcounts."""
+    import orbx
+    import orbx_synth
+    n = 5800
+    assert n * n * 2 > 64 << 20
+    q = orbx_synth.random_descriptors(n, 71)
+    t = orbx_synth.random_descriptors(n, 72)
+    full = orbx.allpairs_host(q, t, orbx.FULL_U16)
+    assert full.shape == (n, n) and full.dtype == np.uint16
+    rows = np.unique(np.concatenate([np.arange(0, n, 19), [n - 1]]))
+    popcount = np.array([bin(i).count("1") for i in range(256)], np.uint16)
+    want = popcount[q[rows, None, :] ^ t[None, :, :]].sum(axis=-1, dtype=np.uint16)
+    assert len(rows) > 300 and np.array_equal(full[rows], want)

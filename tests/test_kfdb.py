@@ -969,3 +969,20 @@ def test_gpu_two_threads(cuda):
         assert cand in allowed[qi], (qi, cand)
     final, _ = ref.detect_reloc(queries[0], None)
     assert results[-3] == (0, tuple(final))                      # the last round ran after the writer finished
+
+
+@pytest.mark.gpu
+def test_gpu_empty_bag_of_words(cuda):
+    """A KeyFrame and a query without words (qn == 0) through orbv_db_add, orbv_db_scores and both detections: the
+    host calls' word and weight tables are single slots the device never reads.  In lockstep with the restatement,
+    as every other query."""
+    rng, kfs, draw = gen_db(61, nkf=5)
+    p = Pair(400)
+    empty = (np.zeros(0, np.int32), np.zeros(0, np.float64))
+    for b in kfs[:3]:
+        p.add(b)
+    assert p.add(empty) == 3 and p.g.info()[:2] == (4, 4)
+    assert p.reloc(empty, None)[0] == [] and p.loop(empty, 0.0, None, None)[0] == []
+    p.scores(empty, [0, 3])
+    p.scores(kfs[0], [3, 0])                                     # the KeyFrame without words, as a slot
+    assert p.reloc(draw(), None)[0]                              # and beside it the others still answer

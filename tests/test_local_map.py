@@ -836,3 +836,16 @@ def test_gpu_chain_local_map_frustum_projection(cuda):
     got = dproj.cpu().numpy().view(orbx.PROJ_POINT_DTYPE).reshape(pcap)[:k]
     assert same_proj(got, proj)
     assert int(nm[0]) == wn and np.array_equal(match.cpu().numpy()[0, :500], wm)
+
+
+@pytest.mark.gpu
+def test_gpu_host_form_empty_tables_and_frames(cuda):
+    """orbm_local_map on host arrays where a table or a list is absent: no MapPoint, no observation, no child and no
+    d_kf_rank; a frame without features; d_frame_outlier absent and given.  Each absent array is one slot the device
+    call never reads; every output against the restatement, as for the other scenes."""
+    E = Table(2, 3, 0)
+    assert E.rank is None and len(E.obs) == 0 and len(E.child) == 0
+    check_host(E, [frame([]), frame([-1, -1], prev=[1], ref=1), frame([-1], ol=[-1])], 4, 4)
+    T, fr, kfcap, pcap, *_ = scene_tie_by_rank()
+    assert T.rank is not None and all(F.ol is None for F in fr)
+    check_host(T, [frame([])] + [frame(F.mp, np.full(len(F.mp), -1, np.int32), F.prev, F.ref) for F in fr], kfcap, pcap)

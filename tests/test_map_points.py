@@ -675,3 +675,18 @@ def test_gpu_refresh_chain_extract_to_fuse(cuda):
     wn, wm = py_fuse(view, pose[0], wpts, wpdesc, pp, 3.0, False)
     assert int(nf[0]) == wn and match.cpu().numpy()[0, :npts].tolist() == wm
     assert wn >= 25
+
+
+@pytest.mark.gpu
+def test_gpu_refresh_host_form_empty_tables(cuda):
+    """orbm_refresh_map_points on host arrays with MapPoints that have no observation (an empty list), and over a
+    KeyFrame table without KeyFrames (nkf == 0): each absent table is one slot the device call never reads, every
+    point reports "no observation" and keeps its bits."""
+    sc = make_scene(5, [0, 0, 0])
+    assert len(sc.obs) == 0
+    none = Scene(sc.kps[:0], sc.desc[:0], sc.counts[:0], sc.pose[:0], sc.bad[:0], sc.obs_ptr, sc.obs, sc.ref, sc.pts,
+                 sc.pdesc)
+    for s in (sc, none):
+        recs = py_refresh(s, MAX_OBS, params())
+        assert [r["status"] for r in recs] == [-1, -1, -1]
+        assert same_result(run_host(3, s), expected(3, s, recs))

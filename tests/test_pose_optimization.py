@@ -852,6 +852,21 @@ def test_gpu_batch(cuda, gi, flags, stride, trace):
 
 
 @pytest.mark.gpu
+def test_gpu_host_entry_empty_frame_and_empty_table(cuda):
+    """A frame without features, over the fixture's MapPoint table and over an empty one: the host form's tables are
+    single slots that the device call never reads.  Against the CPU lane, every field."""
+    import orbx
+    sc = fixtures()["mixed"][0]
+    gp = orbx.PoseParams.from_buffer_copy(params())
+    for pts in (sc["pts"], sc["pts"][:0]):
+        args = (sc["kps"][:0], sc["uright"][:0], sc["frame_mp"][:0], pts, sc["pose"], gp, 1, sc["outlier"][:0])
+        got, lane = orbx.pose_optimization(*args), orbx.pose_optimization(*args, on_host=True)
+        assert got.keys() == lane.keys() and got["status"] == 0 and got["ninliers"] == 0
+        for k in lane:
+            assert np.asarray(got[k]).tobytes() == np.asarray(lane[k]).tobytes(), k
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", ["ncorr2", "mixed", "rejected", "emptied", "turn_y"])
 def test_gpu_host_entry(cuda, name):
     """orbm_pose_optimization on host arrays (one frame per call)."""

@@ -1553,3 +1553,48 @@ def test_gpu_chain_bow_sim3_solver_search_by_sim3(cuda):
         same(device_result(sv, p, n, n), sims[p][2], "solver %d" % p)
         assert int(nf[p]) == wantn[p] and list(m12[p, :n].cpu().numpy()) == list(want12[p]), "SearchBySim3 %d" % p
     assert int(nf[2]) == 0 and (m12[2].cpu().numpy() == -1).all() and not sv.sim3[2].cpu().numpy().any()
+
+
+def grown_pair(extra1, extra2):
+    """sized_reference(63, 5)'s pair with features without a MapPoint (and without a match) appended to KeyFrame 1
+    or 2: the same solver, over KeyFrames of unequal counts."""
+    pr, d, _ = sized_reference(63, 5)
+    pr = dict(pr)
+    for side, extra in (("1", extra1), ("2", extra2)):
+        pad = np.repeat(pr["kps" + side][:1], extra)
+        pr["kps" + side] = np.concatenate([pr["kps" + side], pad])
+        pr["kf_mp" + side] = np.concatenate([pr["kf_mp" + side], np.full(extra, -1, np.int32)])
+    pr["match12"] = np.concatenate([pr["match12"], np.full(extra1, -1, np.int32)])
+    return pr, d, PySolver(pr, params(), min_inl=edge_min_inliers(63)).iterate(5, d)
+
+
+def empty_pair():
+    return {k: (v[:0] if isinstance(v, np.ndarray) and k in ("kps1", "kf_mp1", "kps2", "kf_mp2", "match12") else v)
+            for k, v in make_pair(62, 1).items()}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra1,extra2", [(0, 9), (9, 0)])
+def test_gpu_host_form_unequal_counts(cuda, extra1, extra2):
+    """orbm_sim3_solve lays its two KeyFrames out at stride max(n1, n2): the shorter one's slots past its count are
+    padding (no keypoint, MapPoint -1), on either side."""
+    import orbx
+    pr, d, want = grown_pair(extra1, extra2)
+    assert want["ninliers"] > MIN_INL and len(want["inliers12"]) == 63 + extra1 and len(want["already2"]) == 63 + extra2
+    r = orbx.sim3_solve((pr["kps1"], pr["kf_mp1"]), (pr["kps2"], pr["kf_mp2"]), pr["T1w"], pr["T2w"], pr["pts"],
+                        pr["obs_ptr"], pr["obs"], pr["match12"], d, orbx.PoseParams.from_buffer_copy(params()), 5,
+                        min_inliers=edge_min_inliers(63))
+    same(r, want, "n1 = %d, n2 = %d" % (63 + extra1, 63 + extra2))
+
+
+@pytest.mark.gpu
+def test_gpu_host_form_empty_keyframes(cuda):
+    """Two KeyFrames without features: the host form's blocks are single slots that are never read."""
+    import orbx
+    pr = empty_pair()
+    d = rand_draws(82, 5)
+    want = PySolver(pr, params()).iterate(5, d)
+    r = orbx.sim3_solve((pr["kps1"], pr["kf_mp1"]), (pr["kps2"], pr["kf_mp2"]), pr["T1w"], pr["T2w"], pr["pts"],
+                        pr["obs_ptr"], pr["obs"], pr["match12"], d, orbx.PoseParams.from_buffer_copy(params()), 5)
+    same(r, want, "empty")
+    assert want["nomore"] == 1

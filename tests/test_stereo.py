@@ -227,6 +227,28 @@ def test_gpu_host_stereo_parity(orbref, cuda, W, H, nfeat, seed):
 
 
 @pytest.mark.gpu
+def test_gpu_host_stereo_unequal_counts(orbref, cuda):
+    """The host call lays the two keypoint lists out at stride max(n_l, n_r): lists cut to 120 and 200 keypoints, the
+    shorter one on either side, so that the slots past its count are padding the kernels must not read."""
+    import orbx
+    W, H, nfeat, seed = STEREO_CONFIGS[2]
+    L, R = _pair(seed, W, H)
+    exl = orbx.ORBextractor(nfeat, 1.2, 8, 20, 7)
+    exr = orbx.ORBextractor(nfeat, 1.2, 8, 20, 7)
+    kl, dl = exl(L)
+    kr, dr = exr(R)
+    p = orbref.make_params(nfeat, 1.2, 8, 20, 7)
+    a, b = orbref.extract(L, p), orbref.extract(R, p)
+    assert min(len(kl), len(kr)) >= 200
+    for nl, nr in ((120, 200), (200, 120)):
+        ur, dp, good = orbx.compute_stereo_matches(exl, exr, kl[:nl], dl[:nl], kr[:nr], dr[:nr], EUROC_BF, EUROC_FX)
+        ca = orbref.ExtractResult(a.keypoints[:nl], a.descriptors[:nl], a.pyramid, a.level_counts, a.cand_counts)
+        cb = orbref.ExtractResult(b.keypoints[:nr], b.descriptors[:nr], b.pyramid, b.level_counts, b.cand_counts)
+        wur, wdp, _, wgood = orbref.compute_stereo_matches(p, ca, cb, H, W, EUROC_BF, EUROC_FX)
+        assert good == wgood and np.array_equal(ur, wur) and np.array_equal(dp, wdp)
+
+
+@pytest.mark.gpu
 def test_gpu_batch_stereo_parity(orbref, cuda):
     import torch
     import orbx
@@ -368,6 +390,10 @@ def test_gpu_stereo_band(orbref, cuda, seed):
         got = orbx.stereo_band(kl, dl, kr, dr, 480, sc, lo, hi)
         want = orbref.stereo_band(kl, dl, kr, dr, 480, sc, lo, hi)
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    # fewer left keypoints than right ones (above: more): the left frame's slots past its count are padding
+    got = orbx.stereo_band(kl[:40], dl[:40], kr[:55], dr[:55], 480, sc, 0.0, 110.0)
+    want = orbref.stereo_band(kl[:40], dl[:40], kr[:55], dr[:55], 480, sc, 0.0, 110.0)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
     # empty sides
     bi, bd = orbx.stereo_band(kl, dl, kr[:0], dr[:0], 480, sc, 0.0, 110.0)
     assert np.all(bi == -1) and np.all(bd == 100)

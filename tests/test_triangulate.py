@@ -1074,6 +1074,35 @@ def test_gpu_triangulate_host_form_equals_device_form(cuda, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n1,n2", [(45, 65), (65, 45), (65, 0)])
+def test_gpu_triangulate_host_form_unequal_counts(cuda, n1, n2):
+    """The host form lays its two KeyFrames out at stride max(n1, n2): the shorter one's slots past its count are
+    padding the device call never reads, and a match at or past n2 is out of range."""
+    import orbx
+    tab, match, pa, pb, _ = head(65, 3)
+    a, b = int(pa[0]), int(pb[0])
+    two = Table(tab.kps[[a, b]], [n1, n2], tab.pose[[a, b]], tab.kps_raw[[a, b]], tab.uright[[a, b]], tab.depth[[a, b]])
+    one = np.array([0], np.int32)
+    m = match[:1].copy()
+    m[:, n1:] = -1
+    want = expected(two, one, one + 1, m, py_triangulate(two, one, one + 1, m, params()),
+                    mark=np.zeros((2, tab.cap), np.uint8))
+    h = orbx.triangulate(tab.kps[a, :n1], tab.pose[a], tab.kps[b, :n2], tab.pose[b], m[0, :n1], params(),
+                         kps1_raw=tab.kps_raw[a, :n1], kps2_raw=tab.kps_raw[b, :n2], uright1=tab.uright[a, :n1],
+                         depth1=tab.depth[a, :n1], uright2=tab.uright[b, :n2], depth2=tab.depth[b, :n2],
+                         mark1=np.zeros(n1, np.uint8), mark2=np.zeros(n2, np.uint8),
+                         x3d=np.full((n1, 3), SENT, np.int32).view(np.float32))
+    k = int(want["nnew"][0])
+    assert h["nnew"] == k and (k > 0) == (n2 > 0)
+    assert np.array_equal(h["status"], want["status"][0, :n1]) and same_bits(h["x3d"], want["x3d"][0, :n1])
+    assert np.array_equal(h["new_pts"].view(np.int32).reshape(k, 12), want["new_pts"][0, :k])
+    assert np.array_equal(h["new_obs"].view(np.int32).reshape(k, 2, 2), want["new_obs"][0, :k])
+    assert np.array_equal(h["new_ref"].view(np.int32).reshape(k, 2), want["new_ref"][0, :k])
+    assert np.array_equal(h["new_idx1"], want["new_idx1"][0, :k])
+    assert np.array_equal(h["mark1"], want["mark"][0, :n1]) and np.array_equal(h["mark2"], want["mark"][1, :n2])
+
+
+@pytest.mark.gpu
 def test_gpu_chain_search_triangulate_refresh_search_fuse(cuda, orbref):
     """SearchForTriangulation -> triangulate (marking the views' has_mp) -> refresh on the emitted arrays -> the same
     search again -> Fuse of the new points into a third view, every call on device memory the previous one wrote, no
