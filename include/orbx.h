@@ -302,6 +302,16 @@ orbx_status orbm_search_init_batch_device(const orbx_keypoint* d_kps, const uint
                                           int window, float nnratio, int check_ori,
                                           int* d_matches12, int* d_nmatches, void* stream);
 
+/* Test hook: what the SearchForInitialization launcher does for a call with per-frame capacity `cap`
+ * and `npairs` pairs, computed by the function the launcher itself runs; host arithmetic only, no
+ * kernel is launched.  out[10]: [0] query slices per pair of the top-4 build, [1] the number of
+ * LDS-form greedy launches, [2..4] their level-0 capacities in ascending order (0 = unused),
+ * [5] the device-memory greedy launch's capacity (0 = not launched), [6] the largest level-0 count
+ * the LDS form holds, [7] the level-0 count up to which the grid is rank-sorted (counting sort
+ * above), [8] the F2 grid count up to which the build stages F2 in LDS, [9] the queries one workgroup of
+ * the build takes per sweep (a slice sweeps its pair's queries in steps of [0] * [9]). */
+orbx_status orbm_debug_search_init_plan(int cap, int npairs, int* out);
+
 /* ---- Vocabulary-node searches (SearchByBoW x2, SearchForTriangulation) ----
  * The candidate sets are the shared nodes of two DBoW2::FeatureVector maps
  * (std::map<NodeId, vector<unsigned>>, Thirdparty/DBoW2/DBoW2/FeatureVector.h),

@@ -1709,6 +1709,15 @@ orbx_status orbm_search_for_initialization_device(const orbx_keypoint* d_kps, co
     return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
 }
 
+orbx_status orbm_debug_search_init_plan(int cap, int npairs, int* out)
+{
+    if (cap <= 0 || cap > 32767 || npairs <= 0 || !out) return ORBX_EINVAL;
+    static_assert(sizeof(SiPlan) == 10 * sizeof(int), "orbm_debug_search_init_plan rows are ten ints");
+    const SiPlan P = search_init_plan(cap, npairs);   // host arithmetic only: no device, no launch
+    memcpy(out, &P, sizeof P);
+    return ORBX_OK;
+}
+
 orbx_status orbm_search_init_batch_device(const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_counts,
                                           int nframes, int cap, const int* d_pair_a, const int* d_pair_b, int npairs,
                                           int rows, int cols, int window, float nnratio, int check_ori,

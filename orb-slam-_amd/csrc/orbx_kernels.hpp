@@ -143,6 +143,14 @@ void launch_best2_csr(const uint8_t* q, int nq, const uint8_t* t, const int* ptr
                       int* bi, int* b1, int* b2, hipStream_t s);
 void launch_allpairs_full(const uint8_t* q, int nq, const uint8_t* t, int nt, uint16_t* out, hipStream_t s);
 size_t search_init_scratch_bytes(int nframes, int npairs, int cap);
+// What launch_search_init runs for (cap, npairs): k_si_build's query slices per pair, the level-0 capacities of
+// the k_si_greedy launches (LDS tiers ascending, then the device-memory form's, 0 = not launched) and the
+// thresholds the kernels switch form at, and the queries a k_si_build workgroup takes per sweep (ten ints, the row
+// of orbm_debug_search_init_plan).  search_init_scratch_bytes sizes the device-memory form's buffer from it too
+struct SiPlan {
+    int qsplit, nlds, lds_tier[3], global_cap, lds_max, rank_max, build_lds, build_queries;
+};
+SiPlan search_init_plan(int cap, int npairs);
 // prev: [npairs][cap] float2 vbPrevMatched (window centres in, matched F2 positions out) or NULL
 void launch_search_init(const orbx_keypoint* kps, const uint8_t* desc, const int* counts, int nframes, int cap,
                         const int* pa, const int* pb, int npairs, const orbm_grid& G, int window, float nnratio,

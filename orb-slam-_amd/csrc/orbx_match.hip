@@ -944,14 +944,39 @@ static size_t si_global_stride(int cap) { return (sg_layout(cap).total + 255) & 
 size_t search_init_scratch_bytes(int nframes, int npairs, int cap)
 {
     size_t b = (size_t)nframes * cap * (4 + 8) + (size_t)nframes * 2 * 4 + (size_t)npairs * cap * (4 + 16) + 64 * 7;
-    if (cap > si_lds_max_cap()) b += (size_t)npairs * si_global_stride(cap);
+    if (search_init_plan(cap, npairs).global_cap) b += (size_t)npairs * si_global_stride(cap);
     return b;
+}
+
+// The launcher's choices for one call; launch_search_init runs exactly this, orbm_debug_search_init_plan reports it.
+SiPlan search_init_plan(int cap, int npairs)
+{
+    SiPlan P{};
+    // query slices per pair: about 8 waves per SIMD over the chip, at least 4 queries per wave
+    P.qsplit = std::max(1, std::min((2048 + npairs - 1) / npairs, (cap + 15) / 16));
+    P.lds_max = si_lds_max_cap();
+    P.rank_max = kSiRankMax;
+    P.build_lds = kSiBuildLds;
+    P.build_queries = SI_BUILD_NT / 64 * 16;   // a quad per query: 16 per wave and sweep
+    // tiers by level-0 count: up to 512 (22 KB per workgroup), up to kSiLdsCap (two workgroups per CU), the
+    // LDS maximum, then cap from global memory; a launch whose tier holds no pair costs a few microseconds
+    // (its workgroups return at once)
+    const int ldscap = std::min(cap, P.lds_max);
+    const int tiers[3] = {std::min(cap, kSiGreedySmall), std::min(cap, kSiLdsCap), ldscap};
+    int lo = -1;
+    for (int t = 0; t < 3; ++t) {
+        if (tiers[t] <= lo) continue;
+        P.lds_tier[P.nlds++] = lo = tiers[t];
+    }
+    P.global_cap = cap > lo ? cap : 0;
+    return P;
 }
 
 void launch_search_init(const orbx_keypoint* kps, const uint8_t* desc, const int* counts, int nframes, int cap,
                         const int* pa, const int* pb, int npairs, const orbm_grid& G, int window, float nnratio,
                         int check_ori, float* prev, void* scratch, int* m12, int* nm, hipStream_t s)
 {
+    const SiPlan P = search_init_plan(cap, npairs);
     uint8_t* p = (uint8_t*)scratch;
     auto carve = [&](size_t bytes) {
         uint8_t* r = p;
@@ -966,30 +991,22 @@ void launch_search_init(const orbx_keypoint* kps, const uint8_t* desc, const int
     hipFuncSetAttribute((const void*)k_si_grid, hipFuncAttributeMaxDynamicSharedMemorySize, (int)si_grid_smem(cap));
     hipLaunchKernelGGL(k_si_grid, dim3(nframes), dim3(256), si_grid_smem(cap), s, kps, counts, cap, G, gkeys, gxy, gn);
     const size_t bsmem = si_build_smem_bytes();
-    // query slices per pair: about 8 waves per SIMD over the chip, at least 4 queries per wave
-    const int qsplit = std::max(1, std::min((2048 + npairs - 1) / npairs, (cap + 15) / 16));
-    hipLaunchKernelGGL(k_si_build, dim3(npairs, qsplit), dim3(SI_BUILD_NT), bsmem, s, kps, desc, cap, pa, pb, G,
+    hipLaunchKernelGGL(k_si_build, dim3(npairs, P.qsplit), dim3(SI_BUILD_NT), bsmem, s, kps, desc, cap, pa, pb, G,
                        window, (const float2*)prev, gkeys, gxy, gn, qcnt, qtop);
-    const int ldscap = std::min(cap, si_lds_max_cap());
     hipFuncSetAttribute((const void*)k_si_greedy<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)sg_layout(ldscap).total);
-    // tiers by level-0 count: up to 512 (22 KB per workgroup), up to kSiLdsCap (two workgroups per CU), the
-    // LDS maximum, then cap from global memory; a launch whose tier holds no pair costs a few microseconds
-    // (its workgroups return at once)
-    const int tiers[3] = {std::min(cap, kSiGreedySmall), std::min(cap, kSiLdsCap), ldscap};
+                        (int)sg_layout(P.lds_tier[P.nlds - 1]).total);
     int lo = -1;
-    for (int t = 0; t < 3; ++t) {
-        if (tiers[t] <= lo) continue;
-        hipLaunchKernelGGL(k_si_greedy<false>, dim3(npairs), dim3(256), sg_layout(tiers[t]).total, s, kps, desc,
+    for (int t = 0; t < P.nlds; ++t) {
+        hipLaunchKernelGGL(k_si_greedy<false>, dim3(npairs), dim3(256), sg_layout(P.lds_tier[t]).total, s, kps, desc,
                            counts, cap, pa, pb, G, window, nnratio, check_ori, (float2*)prev, gkeys, gxy, gn, qcnt,
-                           qtop, m12, nm, tiers[t], lo, (uint8_t*)nullptr, (size_t)0);
-        lo = tiers[t];
+                           qtop, m12, nm, P.lds_tier[t], lo, (uint8_t*)nullptr, (size_t)0);
+        lo = P.lds_tier[t];
     }
-    if (cap > lo) {
+    if (P.global_cap) {
         uint8_t* gbuf = carve((size_t)npairs * si_global_stride(cap));
         hipLaunchKernelGGL(k_si_greedy<true>, dim3(npairs), dim3(256), 0, s, kps, desc, counts, cap, pa, pb, G, window,
-                           nnratio, check_ori, (float2*)prev, gkeys, gxy, gn, qcnt, qtop, m12, nm, cap, lo, gbuf,
-                           si_global_stride(cap));
+                           nnratio, check_ori, (float2*)prev, gkeys, gxy, gn, qcnt, qtop, m12, nm, P.global_cap, lo,
+                           gbuf, si_global_stride(cap));
     }
 }
 

@@ -41,6 +41,7 @@ EXPORTED = [
     "orbx_extract_batch_device", "orbx_extract_stage_device", "orbx_sync", "orbx_set_timing", "orbx_get_stage_times",
     "orbx_debug_pyramid", "orbx_debug_candidates", "orbx_debug_fill_workspace", "orbx_debug_launches", "orbx_debug_qt_plan", "orbm_descriptor_distance", "orbm_allpairs_device", "orbm_allpairs",
     "orbm_search_init_batch_device", "orbm_search_for_initialization_device", "orbm_search_for_initialization",
+    "orbm_debug_search_init_plan",
     "orbx_compute_stereo_matches", "orbx_stereo_batch_device",
     "orbm_bow_search_device", "orbm_bow_search",
     "orbm_search_by_projection_device", "orbm_search_by_projection",
@@ -125,6 +126,21 @@ def frame_grid(bounds):
     g.grid_w_inv = float(np.float32(64) / np.float32(b[1] - b[0]))
     g.grid_h_inv = float(np.float32(48) / np.float32(b[3] - b[2]))
     return g
+
+
+def debug_search_init_plan(cap, npairs):
+    """What the SearchForInitialization launcher does for per-frame capacity `cap` and `npairs` pairs
+    (orbm_debug_search_init_plan; host arithmetic, no launch): qsplit = k_si_build's query slices per pair,
+    lds_tiers = the level-0 capacities of the LDS-form k_si_greedy launches in ascending order, global_cap = the
+    device-memory form's capacity (0 = not launched), lds_max = the largest level-0 count the LDS form holds,
+    rank_max = k_si_grid's rank sort / counting sort threshold, build_lds = k_si_build's LDS staging threshold, build_queries = the queries one k_si_build
+    workgroup takes per sweep."""
+    out = (C.c_int * 10)()
+    _check("orbm_debug_search_init_plan", lib.orbm_debug_search_init_plan(cap, npairs, out))
+    v = list(out)
+    return {"qsplit": v[0], "lds_tiers": v[2:2 + v[1]], "global_cap": v[5], "lds_max": v[6], "rank_max": v[7],
+            "build_lds": v[8], "build_queries": v[9]}
+
 
 MAP_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
                             ("max_dist", "<f4"), ("min_dist", "<f4"), ("angle", "<f4"), ("octave", "<i4"),
@@ -227,6 +243,7 @@ def _load():
                                                         C.c_int, C.c_float, C.c_int, vp, vp, vp, vp]
     L.orbm_search_for_initialization.argtypes = [C.c_int, vp, u8p, C.c_int, vp, u8p, C.c_int, vp, f32p, C.c_int,
                                                  C.c_float, C.c_int, i32p, i32p]
+    L.orbm_debug_search_init_plan.argtypes = [C.c_int, C.c_int, i32p]
     L.orbx_compute_stereo_matches.argtypes = [vp, vp, vp, u8p, C.c_int, vp, u8p, C.c_int, C.c_float, C.c_float,
                                               f32p, f32p, i32p]
     L.orbx_stereo_batch_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_float, C.c_float, vp, vp,
