@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "orbx_device.hpp"
+#include "orbx_host.hpp"
 #include "orbx_kernels.hpp"
 
 namespace orbx {
@@ -304,9 +305,9 @@ __global__ __launch_bounds__(256) void k_bow_rot(int mode, const orbm_bow_view* 
     if (tid == 0) nmatches[p] = s_n;
 }
 
-void launch_bow(int mode, const orbm_bow_view* v1, const orbm_bow_view* v2, const orbm_triang_params* tp,
-                int npairs, int max_nodes1, float nnratio, int check_ori, int* match, int* bins, int stride,
-                int* nmatches, hipStream_t s)
+static void launch_bow(int mode, const orbm_bow_view* v1, const orbm_bow_view* v2, const orbm_triang_params* tp,
+                       int npairs, int max_nodes1, float nnratio, int check_ori, int* match, int* bins, int stride,
+                       int* nmatches, hipStream_t s)
 {
     hipMemsetAsync(match, 0xFF, sizeof(int) * (size_t)npairs * stride, s);   // -1
     hipMemsetAsync(bins, 0xFF, sizeof(int) * (size_t)npairs * stride, s);
@@ -317,4 +318,106 @@ void launch_bow(int mode, const orbm_bow_view* v1, const orbm_bow_view* v2, cons
                        nmatches);
 }
 
+namespace {
+
+bool bow_view_ok(const orbm_bow_view* v)
+{
+    if (!v || v->n < 0 || v->fv_nnodes < 0 || v->n > ORBM_MAX_FEATURES) return false;
+    if (v->n > 0 && (!v->kps || !v->desc)) return false;
+    if (v->fv_nnodes > 0 && (!v->fv_node || !v->fv_ptr || !v->fv_idx)) return false;
+    for (int k = 0; k < v->fv_nnodes; ++k) {
+        if (v->fv_ptr[k] > v->fv_ptr[k + 1] || (k > 0 && v->fv_node[k] <= v->fv_node[k - 1])) return false;
+        for (int j = v->fv_ptr[k]; j < v->fv_ptr[k + 1]; ++j)
+            if (v->fv_idx[j] < 0 || v->fv_idx[j] >= v->n) return false;
+    }
+    return v->fv_nnodes == 0 || v->fv_ptr[0] == 0;
+}
+
+// blocks of one staged view (device pointers are patched in after the buffers are sized)
+struct BowBlks {
+    Blk<orbx_keypoint> kps;
+    Blk<uint8_t> desc, mp;
+    Blk<float> ur;
+    Blk<int32_t> node, ptr, idx;
+};
+
+BowBlks bow_stage(HostCall& c, const orbm_bow_view* v)
+{
+    const size_t n = (size_t)v->n, nn = (size_t)v->fv_nnodes;
+    BowBlks o;
+    o.kps = c.in(v->kps, n);
+    o.desc = c.in(v->desc, 32 * n);
+    if (v->has_mp) o.mp = c.in(v->has_mp, n);
+    if (v->u_right) o.ur = c.in(v->u_right, n);
+    o.node = c.in(v->fv_node, nn);
+    o.ptr = c.in(v->fv_ptr, nn + 1);
+    o.idx = c.in(v->fv_idx, (size_t)(nn ? v->fv_ptr[nn] : 0));
+    return o;
+}
+
+orbm_bow_view bow_device_view(const HostCall& c, const BowBlks& o, const orbm_bow_view* v)
+{
+    orbm_bow_view d = *v;
+    d.kps = c.dev(o.kps);
+    d.desc = c.dev(o.desc);
+    d.has_mp = v->has_mp ? c.dev(o.mp) : nullptr;
+    d.u_right = v->u_right ? c.dev(o.ur) : nullptr;
+    d.fv_node = c.dev(o.node);
+    d.fv_ptr = c.dev(o.ptr);
+    d.fv_idx = c.dev(o.idx);
+    return d;
+}
+
+}  // namespace
+
 }  // namespace orbx
+
+using namespace orbx;
+
+extern "C" {
+
+orbx_status orbm_bow_search_device(int mode, const orbm_bow_view* d_view1, const orbm_bow_view* d_view2,
+                                   const orbm_triang_params* d_tp, int npairs, int max_nodes1, float nnratio,
+                                   int check_ori, int* d_match, int match_stride, int* d_nmatches, void* stream)
+{
+    if (mode < ORBM_BOW_KF_F || mode > ORBM_TRIANGULATION || !d_view1 || !d_view2 || npairs < 0 ||
+        max_nodes1 < 0 || !d_match || match_stride <= 0 || !d_nmatches || (mode == ORBM_TRIANGULATION && !d_tp))
+        return ORBX_EINVAL;
+    if (npairs == 0) return ORBX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    return with_scratch(sizeof(int) * (size_t)npairs * match_stride, s, [&](void* bins) {
+        launch_bow(mode, d_view1, d_view2, d_tp, npairs, max_nodes1, nnratio, check_ori, d_match, (int*)bins,
+                   match_stride, d_nmatches, s);
+    });
+}
+
+orbx_status orbm_bow_search(int device, int mode, const orbm_bow_view* view1, const orbm_bow_view* view2,
+                            const orbm_triang_params* tp, float nnratio, int check_ori, int* match, int* nmatches)
+{
+    if (mode < ORBM_BOW_KF_F || mode > ORBM_TRIANGULATION || !bow_view_ok(view1) || !bow_view_ok(view2) ||
+        !nmatches || (mode == ORBM_TRIANGULATION && !tp))
+        return ORBX_EINVAL;
+    const int nout = mode == ORBM_BOW_KF_F ? view2->n : view1->n;
+    if (nout > 0 && !match) return ORBX_EINVAL;
+    *nmatches = 0;
+    if (nout == 0) return ORBX_OK;
+    HostCall c(device);
+    // the two device view structs (+ tp) first: they are patched after the buffers are sized
+    const auto ov = c.stage<orbm_bow_view>(2);
+    const auto otp = c.in(tp, tp ? 1 : 0);
+    const BowBlks o1 = bow_stage(c, view1), o2 = bow_stage(c, view2);
+    const auto om = c.out<int>((size_t)nout + 1);   // nmatches, match
+    orbx_status rc = c.prepare();
+    if (rc != ORBX_OK) return rc;
+    c.host(ov)[0] = bow_device_view(c, o1, view1);
+    c.host(ov)[1] = bow_device_view(c, o2, view2);
+    if ((rc = c.upload()) != ORBX_OK) return rc;
+    rc = orbm_bow_search_device(mode, c.dev(ov), c.dev(ov, 1), c.dev(otp), 1, view1->fv_nnodes, nnratio, check_ori,
+                                c.dev(om, 1), nout, c.dev(om), c.stream());
+    if (rc != ORBX_OK) return rc;
+    c.fetch(om, match, (size_t)nout, 1);
+    c.fetch(om, nmatches, 1);
+    return c.finish();
+}
+
+}  // extern "C"

@@ -145,7 +145,7 @@ __device__ __forceinline__ bool nms_keep(const uint8_t* m, uint32_t t1)
 // dword kl of row u * rpp + rl (nd = dwords per ROI row) at its exact byte, so a pass costs one register.
 // LD passes are prefetched (the launch's largest ROI: 8 for
 // 38 x 39, 10 for 38 x 46 ROIs); bigger ROIs load their remainder synchronously.
-// kCellsPerWave (orbx_kernels.hpp) cells per wave: the next cell's ROI loads fly under this one's passes
+// kCellsPerWave (orbx_geom.hpp) cells per wave: the next cell's ROI loads fly under this one's passes
 
 template <int LD>
 struct FastPrefetch {

@@ -17,6 +17,35 @@ constexpr int kEdge = 19;                 // EDGE_THRESHOLD, src/ORBextractor.cc
 constexpr int kMinBorder = kEdge - 3;     // minBorderX/Y, src/ORBextractor.cc:932
 constexpr int kKpCoordBits = 24;          // packed keypoint: x (kp_xbits) | y (24 - kp_xbits) | score (8)
 
+// FAST cells per wave above kLatencyMaxBatch (orbx_kernels.hpp).  Every level's cell list is padded with empty
+// cells to a multiple of it, so a wave's cells share one level and its candidates land in that level's slot region.
+#ifndef ORBX_FAST_CPW
+#define ORBX_FAST_CPW 3
+#endif
+constexpr int kCellsPerWave = ORBX_FAST_CPW;
+// quadtree workgroup size and keypoints held in registers per thread at level l (the rest spill
+// to global): level 0 holds most candidates, levels >= 2 a few hundred
+// (level 0: 16 per thread, or 24 for frames above kQtBigArea pixels, whose level-0 candidates
+// would otherwise mostly spill; the 24-wide kernel's 178 VGPRs crowd co-running waves, so
+// smaller frames keep 16)
+constexpr long long kQtBigArea = 1000000;
+
+// OpenCV x86 builds run cv::resize INTER_LINEAR's vertical pass as VResizeLinearVec_32s8u (SSE2) over a dst row's
+// first rz_simd_end(w) bytes: 16 at a time while x <= w - 16, then 4 at a time while x < w - 4; the scalar loop
+// finishes the 0..4-byte tail (imgproc/src/resize.cpp)
+inline int rz_simd_end(int w)
+{
+    int x = 0;
+    while (x <= w - 16) x += 16;
+    while (x < w - 4) x += 4;
+    return x;
+}
+
+// One entry of the cv::resize coefficient tables (orbx_plan.hpp resize_tables); the kernels read it as an int2
+struct Tap {
+    int x, y;
+};
+
 // One FAST cell ROI (src/ORBextractor.cc:952-976), level coordinates.
 struct Cell {
     int16_t level, roi_w, roi_h, pad;

@@ -149,4 +149,15 @@ private:
     void get(size_t off, void* dst, size_t bytes);
 };
 
+// run(scratch) with `bytes` of stream-ordered scratch, freed behind it on the stream; maps the last error
+template <class Run>
+orbx_status with_scratch(size_t bytes, hipStream_t s, Run run)
+{
+    void* scratch = nullptr;
+    if (hipMallocAsync(&scratch, bytes, s) != hipSuccess) return ORBX_ENOMEM;
+    run(scratch);
+    hipFreeAsync(scratch, s);
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+}
+
 }  // namespace orbx

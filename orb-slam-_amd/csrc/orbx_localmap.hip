@@ -49,7 +49,14 @@ enum { kLmNList = 0, kLmStatus = 1, kLmRef = 2, kLmKeep = 3, kLmTotal = 4, kLmHd
 
 static_assert(ORBM_LOCAL_MAP_LDS_KEYFRAMES * sizeof(int) <= 32768, "the LDS vote counters");
 
-LmLayout lm_layout(int nkf, int nmp, int nframes, int kfcap)
+// The caller's scratch of orbm_local_map_device (orbx_localmap.hip), offsets and strides in ints: the rank table
+// [nkf], then per frame a header (8), the KeyFrame list [kfcap] and the entries per KeyFrame [kfcap] -- small, and
+// cleared by one memset per call (small_bytes) -- then per frame the vote counters [nkf], the first-occurrence keys
+// [nmp] and the frame's MapPoint bitmap [(nmp + 31) / 32], which the kernels put back to zero entry by entry.
+struct LmLayout {
+    size_t inv, hdr, hstride, big, bstride, small_bytes, bytes;
+};
+static LmLayout lm_layout(int nkf, int nmp, int nframes, int kfcap)
 {
     LmLayout L;
     L.inv = 0;

@@ -9,8 +9,10 @@
 #include <limits.h>
 
 #include <algorithm>
+#include <cstring>
 
 #include "orbx_device.hpp"
+#include "orbx_host.hpp"
 #include "orbx_kernels.hpp"
 
 namespace orbx {
@@ -84,8 +86,8 @@ __global__ void k_allpairs_merge(const int* __restrict__ part, int nq, int nspli
     b2_out[qi] = B2;
 }
 
-void launch_allpairs_top2(const uint8_t* q, int nq, const uint8_t* t, int nt, int* bi, int* b1, int* b2,
-                          int* part, int nsplit, hipStream_t s)
+static void launch_allpairs_top2(const uint8_t* q, int nq, const uint8_t* t, int nt, int* bi, int* b1, int* b2,
+                                 int* part, int nsplit, hipStream_t s)
 {
     int chunk = (nt + nsplit - 1) / nsplit;
     chunk = (chunk + 255) / 256 * 256;
@@ -176,14 +178,14 @@ __global__ __launch_bounds__(256) void k_best2_csr(const uint4* __restrict__ q, 
     b2[i] = second;
 }
 
-void launch_best2_csr(const uint8_t* q, int nq, const uint8_t* t, const int* ptr, const int* idx, int tie_last,
-                      int* bi, int* b1, int* b2, hipStream_t s)
+static void launch_best2_csr(const uint8_t* q, int nq, const uint8_t* t, const int* ptr, const int* idx, int tie_last,
+                             int* bi, int* b1, int* b2, hipStream_t s)
 {
     hipLaunchKernelGGL(k_best2_csr, dim3((nq + 255) / 256), dim3(256), 0, s, (const uint4*)q, nq, (const uint4*)t, ptr,
                        idx, tie_last, bi, b1, b2);
 }
 
-void launch_allpairs_full(const uint8_t* q, int nq, const uint8_t* t, int nt, uint16_t* out, hipStream_t s)
+static void launch_allpairs_full(const uint8_t* q, int nq, const uint8_t* t, int nt, uint16_t* out, hipStream_t s)
 {
     dim3 grid((nt + 1023) / 1024, (nq + 63) / 64);
     hipLaunchKernelGGL(k_allpairs_full, grid, dim3(256), 0, s, (const ulonglong2*)q, nq, (const ulonglong2*)t, nt,
@@ -941,7 +943,16 @@ static int si_lds_max_cap()
 
 static size_t si_global_stride(int cap) { return (sg_layout(cap).total + 255) & ~(size_t)255; }
 
-size_t search_init_scratch_bytes(int nframes, int npairs, int cap)
+// What launch_search_init runs for (cap, npairs): k_si_build's query slices per pair, the level-0 capacities of
+// the k_si_greedy launches (LDS tiers ascending, then the device-memory form's, 0 = not launched) and the
+// thresholds the kernels switch form at, and the queries a k_si_build workgroup takes per sweep (ten ints, the row
+// of orbm_debug_search_init_plan).  search_init_scratch_bytes sizes the device-memory form's buffer from it too
+struct SiPlan {
+    int qsplit, nlds, lds_tier[3], global_cap, lds_max, rank_max, build_lds, build_queries;
+};
+static SiPlan search_init_plan(int cap, int npairs);
+
+static size_t search_init_scratch_bytes(int nframes, int npairs, int cap)
 {
     size_t b = (size_t)nframes * cap * (4 + 8) + (size_t)nframes * 2 * 4 + (size_t)npairs * cap * (4 + 16) + 64 * 7;
     if (search_init_plan(cap, npairs).global_cap) b += (size_t)npairs * si_global_stride(cap);
@@ -949,7 +960,7 @@ size_t search_init_scratch_bytes(int nframes, int npairs, int cap)
 }
 
 // The launcher's choices for one call; launch_search_init runs exactly this, orbm_debug_search_init_plan reports it.
-SiPlan search_init_plan(int cap, int npairs)
+static SiPlan search_init_plan(int cap, int npairs)
 {
     SiPlan P{};
     // query slices per pair: about 8 waves per SIMD over the chip, at least 4 queries per wave
@@ -972,9 +983,9 @@ SiPlan search_init_plan(int cap, int npairs)
     return P;
 }
 
-void launch_search_init(const orbx_keypoint* kps, const uint8_t* desc, const int* counts, int nframes, int cap,
-                        const int* pa, const int* pb, int npairs, const orbm_grid& G, int window, float nnratio,
-                        int check_ori, float* prev, void* scratch, int* m12, int* nm, hipStream_t s)
+static void launch_search_init(const orbx_keypoint* kps, const uint8_t* desc, const int* counts, int nframes, int cap,
+                               const int* pa, const int* pb, int npairs, const orbm_grid& G, int window, float nnratio,
+                               int check_ori, float* prev, void* scratch, int* m12, int* nm, hipStream_t s)
 {
     const SiPlan P = search_init_plan(cap, npairs);
     uint8_t* p = (uint8_t*)scratch;
@@ -1011,3 +1022,212 @@ void launch_search_init(const orbx_keypoint* kps, const uint8_t* desc, const int
 }
 
 }  // namespace orbx
+
+using namespace orbx;
+
+extern "C" {
+
+orbx_status orbm_best2_csr_device(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, const int* d_cand_ptr,
+                                  const int* d_cand_idx, int tie_mode, int* d_best_idx, int* d_best, int* d_second,
+                                  void* stream)
+{
+    if (nq < 0 || nt < 0 || (tie_mode != ORBM_TIE_FIRST && tie_mode != ORBM_TIE_LAST)) return ORBX_EINVAL;
+    if (nq == 0) return ORBX_OK;
+    if (!d_q || !d_cand_ptr || !d_best_idx || !d_best || !d_second || (nt > 0 && (!d_t || !d_cand_idx)))
+        return ORBX_EINVAL;
+    launch_best2_csr(d_q, nq, d_t, d_cand_ptr, d_cand_idx, tie_mode == ORBM_TIE_LAST, d_best_idx, d_best, d_second,
+                     (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+}
+
+orbx_status orbm_best2_csr(int device, const uint8_t* q, int nq, const uint8_t* t, int nt, const int* cand_ptr,
+                           const int* cand_idx, int tie_mode, int* best_idx, int* best, int* second)
+{
+    if (nq < 0 || nt < 0 || (tie_mode != ORBM_TIE_FIRST && tie_mode != ORBM_TIE_LAST)) return ORBX_EINVAL;
+    if (nq == 0) return ORBX_OK;
+    if (!q || !cand_ptr || !best_idx || !best || !second) return ORBX_EINVAL;
+    const int ncand = cand_ptr[nq];
+    if (cand_ptr[0] != 0 || ncand < 0 || (ncand > 0 && (!cand_idx || !t))) return ORBX_EINVAL;
+    for (int i = 0; i < nq; ++i)
+        if (cand_ptr[i + 1] < cand_ptr[i]) return ORBX_EINVAL;
+    for (int k = 0; k < ncand; ++k)
+        if (cand_idx[k] < 0 || cand_idx[k] >= nt) return ORBX_EINVAL;
+    HostCall c(device);
+    const size_t Q = (size_t)nq;
+    const auto oq = c.in(q, 32 * Q);
+    const auto ot = c.in(t, (size_t)32 * nt);
+    const auto op = c.in(cand_ptr, Q + 1);
+    const auto oi = c.in(cand_idx, (size_t)ncand);
+    const auto oo = c.out<int>(3 * Q);   // best_idx, best, second
+    orbx_status rc = c.begin();
+    if (rc != ORBX_OK) return rc;
+    rc = orbm_best2_csr_device(c.dev(oq), nq, c.dev(ot), nt, c.dev(op), c.dev(oi), tie_mode, c.dev(oo), c.dev(oo, Q),
+                               c.dev(oo, 2 * Q), c.stream());
+    if (rc != ORBX_OK) return rc;
+    c.fetch(oo, best_idx, Q);
+    c.fetch(oo, best, Q, Q);
+    c.fetch(oo, second, Q, 2 * Q);
+    return c.finish();
+}
+
+int orbm_descriptor_distance(const uint8_t* a, const uint8_t* b)
+{
+    int d = 0;
+    for (int i = 0; i < 4; ++i) {
+        uint64_t x, y;
+        std::memcpy(&x, a + 8 * i, 8);
+        std::memcpy(&y, b + 8 * i, 8);
+        d += __builtin_popcountll(x ^ y);
+    }
+    return d;
+}
+
+orbx_status orbm_allpairs_device(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int mode, int* d_best_idx,
+                                 int* d_best, int* d_second, uint16_t* d_full, void* stream)
+{
+    if (!d_q || !d_t || nq < 0 || nt < 0) return ORBX_EINVAL;
+    if (nq == 0 || nt == 0) return ORBX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == ORBM_TOP2) {
+        if (!d_best_idx || !d_best || !d_second) return ORBX_EINVAL;
+        int nsplit = std::max(1, std::min(64, (256 * 4) / std::max(1, (nq + 255) / 256)));
+        nsplit = std::min(nsplit, (nt + 255) / 256);
+        int* part = nullptr;
+        if (hipMallocAsync((void**)&part, sizeof(int) * 3 * (size_t)nq * nsplit, s) != hipSuccess) return ORBX_ENOMEM;
+        launch_allpairs_top2(d_q, nq, d_t, nt, d_best_idx, d_best, d_second, part, nsplit, s);
+        hipFreeAsync(part, s);
+    } else if (mode == ORBM_FULL_U16) {
+        if (!d_full) return ORBX_EINVAL;
+        launch_allpairs_full(d_q, nq, d_t, nt, d_full, s);
+    } else {
+        return ORBX_EINVAL;
+    }
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+}
+
+orbx_status orbm_allpairs(int device, const uint8_t* q, int nq, const uint8_t* t, int nt, int mode, int* best_idx,
+                          int* best, int* second, uint16_t* full)
+{
+    if (nq < 0 || nt < 0 || (mode != ORBM_TOP2 && mode != ORBM_FULL_U16)) return ORBX_EINVAL;
+    if (nq == 0) return ORBX_OK;
+    if (!q || (nt > 0 && !t)) return ORBX_EINVAL;
+    if (mode == ORBM_TOP2 && (!best_idx || !best || !second)) return ORBX_EINVAL;
+    if (mode == ORBM_FULL_U16 && !full) return ORBX_EINVAL;
+    if (nt == 0) {
+        if (mode == ORBM_TOP2)
+            for (int i = 0; i < nq; ++i) {
+                best_idx[i] = -1;
+                best[i] = second[i] = 256;
+            }
+        return ORBX_OK;
+    }
+    HostCall c(device);
+    const bool top2 = mode == ORBM_TOP2;
+    const size_t Q = (size_t)nq, nfull = top2 ? 0 : Q * (size_t)nt;
+    const auto oq = c.in(q, 32 * Q);
+    const auto ot = c.in(t, (size_t)32 * nt);
+    const auto oo = c.out<int>(top2 ? 3 * Q : 0);   // best_idx, best, second
+    const auto of = c.out<uint16_t>(nfull);         // the other mode's block is one unused slot, and not passed on
+    orbx_status rc = c.begin();
+    if (rc != ORBX_OK) return rc;
+    if (top2)
+        rc = orbm_allpairs_device(c.dev(oq), nq, c.dev(ot), nt, mode, c.dev(oo), c.dev(oo, Q), c.dev(oo, 2 * Q),
+                                  nullptr, c.stream());
+    else
+        rc = orbm_allpairs_device(c.dev(oq), nq, c.dev(ot), nt, mode, nullptr, nullptr, nullptr, c.dev(of),
+                                  c.stream());
+    if (rc != ORBX_OK) return rc;
+    if (top2) {
+        c.fetch(oo, best_idx, Q);
+        c.fetch(oo, best, Q, Q);
+        c.fetch(oo, second, Q, 2 * Q);
+    } else {
+        c.fetch(of, full, nfull);
+    }
+    return c.finish();
+}
+
+orbx_status orbm_search_for_initialization_device(const orbx_keypoint* d_kps, const uint8_t* d_desc,
+                                                  const int* d_counts, int nframes, int cap, const int* d_pair_a,
+                                                  const int* d_pair_b, int npairs, const orbm_grid* grid,
+                                                  int window, float nnratio, int check_ori, float* d_prev_matched,
+                                                  int* d_matches12, int* d_nmatches, void* stream)
+{
+    if (!d_kps || !d_desc || !d_counts || nframes <= 0 || cap <= 0 || cap > 32767 || npairs < 0 || !grid)
+        return ORBX_EINVAL;
+    if (npairs == 0) return ORBX_OK;
+    if (!d_pair_a || !d_pair_b || !d_matches12 || !d_nmatches) return ORBX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    void* scratch = nullptr;
+    if (hipMallocAsync(&scratch, search_init_scratch_bytes(nframes, npairs, cap), s) != hipSuccess)
+        return ORBX_ENOMEM;
+    launch_search_init(d_kps, d_desc, d_counts, nframes, cap, d_pair_a, d_pair_b, npairs, *grid, window, nnratio,
+                       check_ori, d_prev_matched, scratch, d_matches12, d_nmatches, s);
+    hipFreeAsync(scratch, s);
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+}
+
+orbx_status orbm_debug_search_init_plan(int cap, int npairs, int* out)
+{
+    if (cap <= 0 || cap > 32767 || npairs <= 0 || !out) return ORBX_EINVAL;
+    static_assert(sizeof(SiPlan) == 10 * sizeof(int), "orbm_debug_search_init_plan rows are ten ints");
+    const SiPlan P = search_init_plan(cap, npairs);   // host arithmetic only: no device, no launch
+    memcpy(out, &P, sizeof P);
+    return ORBX_OK;
+}
+
+orbx_status orbm_search_init_batch_device(const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_counts,
+                                          int nframes, int cap, const int* d_pair_a, const int* d_pair_b, int npairs,
+                                          int rows, int cols, int window, float nnratio, int check_ori,
+                                          int* d_matches12, int* d_nmatches, void* stream)
+{
+    if (rows <= 0 || cols <= 0) return ORBX_EINVAL;
+    // Frame::ComputeImageBounds without distortion (src/Frame.cc:614-620) and the grid scale (:127-128)
+    const orbm_grid g{0.0f, 0.0f, 64.0f / ((float)cols - 0.0f), 48.0f / ((float)rows - 0.0f)};
+    return orbm_search_for_initialization_device(d_kps, d_desc, d_counts, nframes, cap, d_pair_a, d_pair_b, npairs,
+                                                 &g, window, nnratio, check_ori, nullptr, d_matches12, d_nmatches,
+                                                 stream);
+}
+
+orbx_status orbm_search_for_initialization(int device, const orbx_keypoint* kps1, const uint8_t* desc1, int n1,
+                                           const orbx_keypoint* kps2, const uint8_t* desc2, int n2,
+                                           const orbm_grid* grid, float* prev_matched, int window, float nnratio,
+                                           int check_ori, int* matches12, int* nmatches)
+{
+    if (n1 < 0 || n2 < 0 || n1 > 32767 || n2 > 32767 || !grid || !nmatches) return ORBX_EINVAL;
+    *nmatches = 0;
+    if (n1 == 0) return ORBX_OK;   // vnMatches12 is empty
+    if (!kps1 || !desc1 || !prev_matched || !matches12 || (n2 > 0 && (!kps2 || !desc2))) return ORBX_EINVAL;
+    // extractor order (ORBextractor::operator() concatenates the levels, src/ORBextractor.cc:1290-1333): the
+    // device finds level 0 as a prefix
+    for (int i = 1; i < n1; ++i)
+        if (kps1[i].octave < kps1[i - 1].octave) return ORBX_EINVAL;
+    for (int i = 1; i < n2; ++i)
+        if (kps2[i].octave < kps2[i - 1].octave) return ORBX_EINVAL;
+    for (int i = 0; i < n1; ++i) matches12[i] = -1;
+    if (n2 == 0) return ORBX_OK;   // every GetFeaturesInArea is empty
+    const int cap = std::max(n1, n2);
+    HostCall c(device);
+    const int meta[4] = {n1, n2, 0, 1};   // counts[2], pair (0, 1)
+    const size_t C = (size_t)cap;
+    const auto om = c.in(meta, 4);
+    const auto ok = c.stage<orbx_keypoint>(2 * C);   // frame f at kps + f * cap
+    const auto od = c.stage<uint8_t>(64 * C);
+    const auto opv = c.in(prev_matched, 2 * (size_t)n1);   // copied back after the matches, hence not inout()
+    const auto ores = c.out<int>(C + 1);             // nmatches, matches12
+    const auto osc = c.out<uint8_t>(search_init_scratch_bytes(2, 1, cap));
+    orbx_status rc = c.prepare();
+    if (rc != ORBX_OK) return rc;
+    pack_pair(c.host(ok), C, kps1, (size_t)n1, kps2, (size_t)n2);
+    pack_pair(c.host(od), 32 * C, desc1, (size_t)32 * n1, desc2, (size_t)32 * n2);
+    if ((rc = c.upload()) != ORBX_OK) return rc;
+    launch_search_init(c.dev(ok), c.dev(od), c.dev(om), 2, cap, c.dev(om, 2), c.dev(om, 3), 1, *grid, window, nnratio,
+                       check_ori, c.dev(opv), c.dev(osc), c.dev(ores, 1), c.dev(ores), c.stream());
+    if (hipGetLastError() != hipSuccess) return ORBX_EDEVICE;
+    c.fetch(ores, matches12, (size_t)n1, 1);
+    c.fetch(ores, nmatches, 1);
+    c.fetch(opv, prev_matched, opv.n);
+    return c.finish();
+}
+
+}  // extern "C"

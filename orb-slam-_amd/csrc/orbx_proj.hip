@@ -27,7 +27,11 @@
 // file; the reference's GCC -march=native FMAs are explicit).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstring>
+
 #include "orbx_device.hpp"
+#include "orbx_host.hpp"
 #include "orbx_kernels.hpp"
 
 namespace orbx {
@@ -787,7 +791,7 @@ __global__ __launch_bounds__(64) void k_resolve(const orbx_keypoint* __restrict_
     if (lane == 0) nmatches[f] = count;
 }
 
-size_t proj_scratch_bytes(int nframes, int cap, int pcap)
+static size_t proj_scratch_bytes(int nframes, int cap, int pcap)
 {
     return GridScratch(nullptr, nframes, cap, (size_t)nframes * pcap * sizeof(TopResult)).bytes;
 }
@@ -816,10 +820,10 @@ static void launch_search(const orbx_keypoint* kps, const uint8_t* desc, const f
     }
 }
 
-void launch_proj(const orbx_keypoint* kps, const uint8_t* desc, const float* uright, const uint8_t* claimed,
-                 const int* counts, int nframes, int cap, const orbm_proj_point* pts, const uint8_t* pdesc,
-                 const int* npts, int pcap, const orbm_proj_params& P, void* scratch, int* match, int* nmatches,
-                 hipStream_t s)
+static void launch_proj(const orbx_keypoint* kps, const uint8_t* desc, const float* uright, const uint8_t* claimed,
+                        const int* counts, int nframes, int cap, const orbm_proj_point* pts, const uint8_t* pdesc,
+                        const int* npts, int pcap, const orbm_proj_params& P, void* scratch, int* match, int* nmatches,
+                        hipStream_t s)
 {
     launch_search<LocalMapSearch>(kps, desc, uright, claimed, counts, nframes, cap, nullptr, pts, pdesc, npts, pcap, P,
                                   scratch, match, nmatches, s);
@@ -838,10 +842,10 @@ static void with_pose_search(int mode, Fn fn)
     }
 }
 
-void launch_pose_search(int mode, const orbx_keypoint* kps, const uint8_t* desc, const float* uright,
-                        const uint8_t* claimed, const int* counts, int nframes, int cap, const float* pose,
-                        const orbm_map_point* pts, const uint8_t* pdesc, const int* npts, int pcap,
-                        const orbm_pose_params& P, void* scratch, int* match, int* nmatches, hipStream_t s)
+static void launch_pose_search(int mode, const orbx_keypoint* kps, const uint8_t* desc, const float* uright,
+                               const uint8_t* claimed, const int* counts, int nframes, int cap, const float* pose,
+                               const orbm_map_point* pts, const uint8_t* pdesc, const int* npts, int pcap,
+                               const orbm_pose_params& P, void* scratch, int* match, int* nmatches, hipStream_t s)
 {
     with_pose_search(mode, [&](auto search) {
         launch_search<decltype(search)>(kps, desc, uright, claimed, counts, nframes, cap, pose, pts, pdesc, npts, pcap,
@@ -990,16 +994,16 @@ __global__ __launch_bounds__(256) void k_s3_agree(const int* __restrict__ match1
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(&nfound[p], n);
 }
 
-size_t sim3_scratch_bytes(int nkf, int npairs, int cap)
+static size_t sim3_scratch_bytes(int nkf, int npairs, int cap)
 {
     return GridScratch(nullptr, nkf, cap, (size_t)2 * npairs * cap * 4).bytes;
 }
 
-void launch_search_by_sim3(const orbx_keypoint* kps, const uint8_t* desc, const orbm_map_point* mps,
-                           const uint8_t* mpdesc, const int* counts, int nkf, int cap, const float* pose,
-                           const int* pair_a, const int* pair_b, const float* sim3, const uint8_t* already1,
-                           const uint8_t* already2, int npairs, const orbm_pose_params& P, void* scratch, int* match12,
-                           int* nfound, int* match1, int* match2, hipStream_t s)
+static void launch_search_by_sim3(const orbx_keypoint* kps, const uint8_t* desc, const orbm_map_point* mps,
+                                  const uint8_t* mpdesc, const int* counts, int nkf, int cap, const float* pose,
+                                  const int* pair_a, const int* pair_b, const float* sim3, const uint8_t* already1,
+                                  const uint8_t* already2, int npairs, const orbm_pose_params& P, void* scratch,
+                                  int* match12, int* nfound, int* match1, int* match2, hipStream_t s)
 {
     const GridScratch sc(scratch, nkf, cap, 0);
     int* tmp = (int*)sc.tail;
@@ -1015,3 +1019,204 @@ void launch_search_by_sim3(const orbx_keypoint* kps, const uint8_t* desc, const 
 }
 
 }  // namespace orbx
+
+using namespace orbx;
+
+extern "C" {
+
+orbx_status orbm_search_by_projection_device(const orbx_keypoint* d_kps, const uint8_t* d_desc, const float* d_uright,
+                                             const uint8_t* d_claimed, const int* d_counts, int nframes, int cap,
+                                             const orbm_proj_point* d_pts, const uint8_t* d_pdesc, const int* d_npts,
+                                             int pcap, const orbm_proj_params* params, int* d_match,
+                                             int* d_nmatches, void* stream)
+{
+    if (!d_kps || !d_desc || !d_uright || !d_claimed || !d_counts || nframes < 0 || cap <= 0 || cap > ORBM_MAX_FEATURES ||
+        !d_pts || !d_pdesc || !d_npts || pcap <= 0 || !params || !d_match || !d_nmatches)
+        return ORBX_EINVAL;
+    if (nframes == 0) return ORBX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    return with_scratch(proj_scratch_bytes(nframes, cap, pcap), s, [&](void* scratch) {
+        launch_proj(d_kps, d_desc, d_uright, d_claimed, d_counts, nframes, cap, d_pts, d_pdesc, d_npts, pcap, *params,
+                    scratch, d_match, d_nmatches, s);
+    });
+}
+
+orbx_status orbm_search_by_projection(int device, const orbx_keypoint* kps, const uint8_t* desc, const float* uright,
+                                      const uint8_t* claimed, int n, const orbm_proj_point* pts, const uint8_t* pdesc,
+                                      int np, const orbm_proj_params* params, int* match, int* nmatches)
+{
+    if (n < 0 || n > ORBM_MAX_FEATURES || np < 0 || !params || !nmatches) return ORBX_EINVAL;
+    *nmatches = 0;
+    if (n == 0) return ORBX_OK;
+    if (!kps || !desc || !uright || !claimed || !match || (np > 0 && (!pts || !pdesc))) return ORBX_EINVAL;
+    for (int i = 0; i < np; ++i)
+        if ((pts[i].flags & 1) && (pts[i].level < 0 || pts[i].level >= 16)) return ORBX_EINVAL;
+    for (int i = 0; i < n; ++i) match[i] = -1;
+    if (np == 0) return ORBX_OK;
+    HostCall c(device);
+    const int cn[2] = {n, np};
+    const auto ocn = c.in(cn, 2);
+    const auto ok = c.in(kps, (size_t)n);
+    const auto od = c.in(desc, (size_t)32 * n);
+    const auto ou = c.in(uright, (size_t)n);
+    const auto oc = c.in(claimed, (size_t)n);
+    const auto op = c.in(pts, (size_t)np);
+    const auto opd = c.in(pdesc, (size_t)32 * np);
+    const auto om = c.out<int>((size_t)n + 1);   // nmatches, match
+    orbx_status rc = c.begin();
+    if (rc != ORBX_OK) return rc;
+    rc = orbm_search_by_projection_device(c.dev(ok), c.dev(od), c.dev(ou), c.dev(oc), c.dev(ocn), 1, n, c.dev(op),
+                                          c.dev(opd), c.dev(ocn, 1), np, params, c.dev(om, 1), c.dev(om), c.stream());
+    if (rc != ORBX_OK) return rc;
+    c.fetch(om, match, (size_t)n, 1);
+    c.fetch(om, nmatches, 1);
+    return c.finish();
+}
+
+orbx_status orbm_project_search_device(int mode, const orbx_keypoint* d_kps, const uint8_t* d_desc,
+                                       const float* d_uright, const uint8_t* d_claimed, const int* d_counts,
+                                       int nframes, int cap, const float* d_pose, const orbm_map_point* d_pts,
+                                       const uint8_t* d_pdesc, const int* d_npts, int pcap,
+                                       const orbm_pose_params* params, int* d_match, int* d_nmatches, void* stream)
+{
+    if (mode < ORBM_PROJ_LAST_FRAME || mode > ORBM_FUSE_SIM3 || !d_kps || !d_desc || !d_uright || !d_claimed ||
+        !d_counts || nframes < 0 || cap <= 0 || cap > ORBM_MAX_FEATURES || !d_pose || !d_pts || !d_pdesc || !d_npts ||
+        pcap <= 0 || !params || !d_match || !d_nmatches || params->nlevels < 1 || params->nlevels > 16)
+        return ORBX_EINVAL;
+    if (nframes == 0) return ORBX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    return with_scratch(proj_scratch_bytes(nframes, cap, pcap), s, [&](void* scratch) {
+        launch_pose_search(mode, d_kps, d_desc, d_uright, d_claimed, d_counts, nframes, cap, d_pose, d_pts, d_pdesc,
+                           d_npts, pcap, *params, scratch, d_match, d_nmatches, s);
+    });
+}
+
+orbx_status orbm_project_search(int device, int mode, const orbx_keypoint* kps, const uint8_t* desc,
+                                const float* uright, const uint8_t* claimed, int n, const float* pose,
+                                const orbm_map_point* pts, const uint8_t* pdesc, int np,
+                                const orbm_pose_params* params, int* match, int* nmatches)
+{
+    if (mode < ORBM_PROJ_LAST_FRAME || mode > ORBM_FUSE_SIM3 || n < 0 || n > ORBM_MAX_FEATURES || np < 0 || !params ||
+        !nmatches || !pose || params->nlevels < 1 || params->nlevels > 16)
+        return ORBX_EINVAL;
+    const bool search = mode <= ORBM_PROJ_SIM3;
+    const int nout = search ? n : np;
+    *nmatches = 0;
+    if (nout > 0 && !match) return ORBX_EINVAL;
+    if ((n > 0 && (!kps || !desc || !uright || (search && !claimed))) || (np > 0 && (!pts || !pdesc)))
+        return ORBX_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (kps[i].octave < 0 || kps[i].octave >= 16) return ORBX_EINVAL;
+    if (mode == ORBM_PROJ_LAST_FRAME)
+        for (int i = 0; i < np; ++i)
+            if ((pts[i].flags & 1) && (pts[i].octave < 0 || pts[i].octave >= 16)) return ORBX_EINVAL;
+    for (int i = 0; i < nout; ++i) match[i] = -1;
+    if (n == 0 || np == 0) return ORBX_OK;
+    HostCall c(device);
+    const int cn[2] = {n, np};
+    const auto ocn = c.in(cn, 2);
+    const auto opo = c.in(pose, 24);
+    const auto ok = c.in(kps, (size_t)n);
+    const auto od = c.in(desc, (size_t)32 * n);
+    const auto ou = c.in(uright, (size_t)n);
+    const auto oc = c.in(search ? claimed : nullptr, (size_t)n);
+    const auto op = c.in(pts, (size_t)np);
+    const auto opd = c.in(pdesc, (size_t)32 * np);
+    const auto om = c.out<int>((size_t)nout + 1);   // nmatches, match
+    orbx_status rc = c.begin();
+    if (rc != ORBX_OK) return rc;
+    rc = orbm_project_search_device(mode, c.dev(ok), c.dev(od), c.dev(ou), c.dev(oc), c.dev(ocn), 1, n, c.dev(opo),
+                                    c.dev(op), c.dev(opd), c.dev(ocn, 1), np, params, c.dev(om, 1), c.dev(om),
+                                    c.stream());
+    if (rc != ORBX_OK) return rc;
+    c.fetch(om, match, (size_t)nout, 1);
+    c.fetch(om, nmatches, 1);
+    return c.finish();
+}
+
+orbx_status orbm_search_by_sim3_device(const orbx_keypoint* d_kps, const uint8_t* d_desc, const orbm_map_point* d_mps,
+                                       const uint8_t* d_mpdesc, const int* d_counts, int nkf, int cap,
+                                       const float* d_pose, const int* d_pair_a, const int* d_pair_b,
+                                       const float* d_sim3, const uint8_t* d_already1, const uint8_t* d_already2,
+                                       int npairs, const orbm_pose_params* params, int* d_match12, int* d_nfound,
+                                       int* d_match1, int* d_match2, void* stream)
+{
+    if (nkf < 0 || npairs < 0 || npairs > 65535 || cap <= 0 || cap > ORBM_MAX_FEATURES || !params ||
+        params->nlevels < 1 || params->nlevels > 16)
+        return ORBX_EINVAL;
+    if (npairs == 0) return ORBX_OK;
+    if (nkf == 0 || !d_kps || !d_desc || !d_mps || !d_mpdesc || !d_counts || !d_pose || !d_pair_a || !d_pair_b ||
+        !d_sim3 || !d_already1 || !d_already2 || !d_match12 || !d_nfound)
+        return ORBX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    return with_scratch(sim3_scratch_bytes(nkf, npairs, cap), s, [&](void* scratch) {
+        launch_search_by_sim3(d_kps, d_desc, d_mps, d_mpdesc, d_counts, nkf, cap, d_pose, d_pair_a, d_pair_b, d_sim3,
+                              d_already1, d_already2, npairs, *params, scratch, d_match12, d_nfound, d_match1,
+                              d_match2, s);
+    });
+}
+
+orbx_status orbm_search_by_sim3(int device, const orbx_keypoint* kps1, const uint8_t* desc1,
+                                const orbm_map_point* mps1, const uint8_t* mpdesc1, const uint8_t* already1, int n1,
+                                const float* T1w, const orbx_keypoint* kps2, const uint8_t* desc2,
+                                const orbm_map_point* mps2, const uint8_t* mpdesc2, const uint8_t* already2, int n2,
+                                const float* T2w, float s12, const float* R12, const float* t12,
+                                const orbm_pose_params* params, int* match12, int* nfound, int* match1, int* match2)
+{
+    if (n1 < 0 || n1 > ORBM_MAX_FEATURES || n2 < 0 || n2 > ORBM_MAX_FEATURES || !params || !nfound || !T1w || !T2w ||
+        !R12 || !t12 || !(s12 > 0.0f) || params->nlevels < 1 || params->nlevels > 16)
+        return ORBX_EINVAL;
+    *nfound = 0;
+    if ((n1 > 0 && (!kps1 || !desc1 || !mps1 || !mpdesc1 || !already1 || !match12)) ||
+        (n2 > 0 && (!kps2 || !desc2 || !mps2 || !mpdesc2 || !already2)))
+        return ORBX_EINVAL;
+    for (int i = 0; i < n1; ++i)
+        if (kps1[i].octave < 0 || kps1[i].octave >= 16) return ORBX_EINVAL;
+    for (int i = 0; i < n2; ++i)
+        if (kps2[i].octave < 0 || kps2[i].octave >= 16) return ORBX_EINVAL;
+    for (int i = 0; i < n1; ++i) match12[i] = -1;
+    if (match1)
+        for (int i = 0; i < n1; ++i) match1[i] = -1;
+    if (match2)
+        for (int i = 0; i < n2; ++i) match2[i] = -1;
+    if (n1 == 0 || n2 == 0) return ORBX_OK;
+    // the two KeyFrames as a batch of two at stride cap
+    const int cap = std::max(n1, n2);
+    const size_t c = (size_t)cap;
+    const int head[4] = {n1, n2, 0, 1};   // d_counts[2], d_pair_a[1], d_pair_b[1]
+    float geo[24 + 13];                    // d_pose[2 * 12], d_sim3[13]
+    std::memcpy(geo, T1w, sizeof(float) * 12);
+    std::memcpy(geo + 12, T2w, sizeof(float) * 12);
+    geo[24] = s12;
+    std::memcpy(geo + 25, R12, sizeof(float) * 9);
+    std::memcpy(geo + 34, t12, sizeof(float) * 3);
+    HostCall hc(device);
+    const auto oh = hc.in(head, 4);
+    const auto og = hc.in(geo, 24 + 13);
+    const auto ok = hc.stage<orbx_keypoint>(2 * c);
+    const auto od = hc.stage<uint8_t>(32 * 2 * c);
+    const auto om = hc.stage<orbm_map_point>(2 * c);
+    const auto omd = hc.stage<uint8_t>(32 * 2 * c);
+    const auto oa = hc.stage<uint8_t>(2 * c);    // already1[cap], already2[cap]
+    const auto oo = hc.out<int>(3 * c + 1);      // nfound, match12, match1, match2
+    orbx_status rc = hc.prepare();
+    if (rc != ORBX_OK) return rc;
+    const size_t m1 = (size_t)n1, m2 = (size_t)n2;
+    pack_pair(hc.host(ok), c, kps1, m1, kps2, m2);
+    pack_pair(hc.host(od), 32 * c, desc1, 32 * m1, desc2, 32 * m2);
+    pack_pair(hc.host(om), c, mps1, m1, mps2, m2);
+    pack_pair(hc.host(omd), 32 * c, mpdesc1, 32 * m1, mpdesc2, 32 * m2);
+    pack_pair(hc.host(oa), c, already1, m1, already2, m2);
+    if ((rc = hc.upload()) != ORBX_OK) return rc;
+    rc = orbm_search_by_sim3_device(hc.dev(ok), hc.dev(od), hc.dev(om), hc.dev(omd), hc.dev(oh), 2, cap, hc.dev(og),
+                                    hc.dev(oh, 2), hc.dev(oh, 3), hc.dev(og, 24), hc.dev(oa), hc.dev(oa, c), 1, params,
+                                    hc.dev(oo, 1), hc.dev(oo), hc.dev(oo, 1 + c), hc.dev(oo, 1 + 2 * c), hc.stream());
+    if (rc != ORBX_OK) return rc;
+    hc.fetch(oo, nfound, 1);
+    hc.fetch(oo, match12, m1, 1);
+    hc.fetch(oo, match1, m1, 1 + c);
+    hc.fetch(oo, match2, m2, 1 + 2 * c);
+    return hc.finish();
+}
+
+}  // extern "C"

@@ -420,7 +420,7 @@ __global__ __launch_bounds__(kPyrMaxNT) void k_pyramid_fused(const Geometry* __r
     }
 }
 
-bool pyr_plan(Geometry& g, const int2* yt, std::vector<int4>& bands)
+bool pyr_plan(Geometry& g, const Tap* yt, std::vector<int4>& bands)
 {
     bands.clear();
     g.pyr_ngroups = 0;

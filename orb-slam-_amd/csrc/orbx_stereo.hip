@@ -11,7 +11,11 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
+#include <algorithm>
+#include <cmath>
+
 #include "orbx_device.hpp"
+#include "orbx_host.hpp"
 #include "orbx_kernels.hpp"
 
 namespace orbx {
@@ -306,6 +310,13 @@ __global__ __launch_bounds__(1024) void k_stereo_cut(const int* __restrict__ cou
     if (tid == 0) ngood[p] = s_good;
 }
 
+constexpr int kStMaxLevels = 32;
+struct StBandArgs {
+    float scale[kStMaxLevels];   // per-octave scale factor, padded with the last level's
+    int nlevels, rows, rband;
+    float minD, maxD;
+};
+
 // S3 k_stereo_band: the coarse stage alone (orbm_stereo_band), for callers that keep their own SAD
 // stage.  Same buckets and search as S1; the scale table comes by value and is staged in LDS.
 __global__ __launch_bounds__(kStNT) void k_stereo_band(StBandArgs A, const orbx_keypoint* __restrict__ kps,
@@ -347,12 +358,11 @@ __global__ __launch_bounds__(kStNT) void k_stereo_band(StBandArgs A, const orbx_
     best_idx[o] = bd < 100 ? (bestKey & 0xFFFF) : -1;
 }
 
-size_t stereo_match_smem(const Geometry& g, int cap) { return stereo_lds_bytes(g.rows, cap); }
+static size_t stereo_band_smem(int rows, int cap) { return stereo_lds_bytes(rows, cap); }
 
-size_t stereo_band_smem(int rows, int cap) { return stereo_lds_bytes(rows, cap); }
-
-void launch_stereo_band(const StBandArgs& a, const orbx_keypoint* kps, const uint8_t* desc, const int* counts, int cap,
-                        const int* fl, const int* fr, int npairs, int* best_idx, int* best_dist, hipStream_t s)
+static void launch_stereo_band(const StBandArgs& a, const orbx_keypoint* kps, const uint8_t* desc, const int* counts,
+                               int cap, const int* fl, const int* fr, int npairs, int* best_idx, int* best_dist,
+                               hipStream_t s)
 {
     const size_t sm = stereo_lds_bytes(a.rows, cap);
     hipFuncSetAttribute((const void*)k_stereo_band, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
@@ -377,3 +387,68 @@ void launch_stereo(const Geometry& g, const Geometry* d_geom, const FramePtrs& P
 }
 
 }  // namespace orbx
+
+using namespace orbx;
+
+extern "C" {
+
+orbx_status orbm_stereo_band_device(const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_counts, int cap,
+                                    const int* d_left, const int* d_right, int npairs, int rows, const float* scale,
+                                    int nlevels, float min_d, float max_d, int* d_best_idx, int* d_best_dist,
+                                    void* stream)
+{
+    if (npairs < 0 || cap < 1 || cap > 65535 || rows < 1 || nlevels < 1 || nlevels > kStMaxLevels || !scale)
+        return ORBX_EINVAL;
+    if (npairs == 0) return ORBX_OK;
+    if (!d_kps || !d_desc || !d_counts || !d_left || !d_right || !d_best_idx || !d_best_dist) return ORBX_EINVAL;
+    if (stereo_band_smem(rows, cap) > 160 * 1024) return ORBX_ENOSPC;
+    StBandArgs a{};
+    float rmax = 0.f;
+    for (int l = 0; l < kStMaxLevels; ++l) {
+        a.scale[l] = scale[std::min(l, nlevels - 1)];
+        if (l < nlevels) rmax = std::max(rmax, 2.0f * scale[l]);
+    }
+    a.nlevels = nlevels;
+    a.rows = rows;
+    a.rband = (int)std::ceil(rmax);
+    a.minD = min_d;
+    a.maxD = max_d;
+    launch_stereo_band(a, d_kps, d_desc, d_counts, cap, d_left, d_right, npairs, d_best_idx, d_best_dist,
+                       (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
+}
+
+orbx_status orbm_stereo_band(int device, const orbx_keypoint* kps_l, const uint8_t* desc_l, int n_l,
+                             const orbx_keypoint* kps_r, const uint8_t* desc_r, int n_r, int rows, const float* scale,
+                             int nlevels, float min_d, float max_d, int* best_idx, int* best_dist)
+{
+    if (n_l < 0 || n_r < 0 || n_l > 65535 || n_r > 65535 || rows < 1 || nlevels < 1 || nlevels > kStMaxLevels ||
+        !scale)
+        return ORBX_EINVAL;
+    if (n_l == 0) return ORBX_OK;
+    if (!kps_l || !desc_l || !best_idx || !best_dist || (n_r > 0 && (!kps_r || !desc_r))) return ORBX_EINVAL;
+    for (int i = 0; i < n_r; ++i)
+        if (kps_r[i].octave < 0 || kps_r[i].octave >= nlevels) return ORBX_EINVAL;
+    const int cap = std::max(n_l, n_r);
+    if (stereo_band_smem(rows, cap) > 160 * 1024) return ORBX_ENOSPC;
+    HostCall c(device);
+    const int meta[4] = {n_l, n_r, 0, 1};   // counts[2], left frame, right frame
+    const size_t C = (size_t)cap;
+    const auto om = c.in(meta, 4);
+    const auto ok = c.stage<orbx_keypoint>(2 * C);   // frame f at kps + f * cap
+    const auto od = c.stage<uint8_t>(64 * C);
+    const auto oo = c.out<int>(2 * C);               // best_idx[cap], best_dist[cap]
+    orbx_status rc = c.prepare();
+    if (rc != ORBX_OK) return rc;
+    pack_pair(c.host(ok), C, kps_l, (size_t)n_l, kps_r, (size_t)n_r);
+    pack_pair(c.host(od), 32 * C, desc_l, (size_t)32 * n_l, desc_r, (size_t)32 * n_r);
+    if ((rc = c.upload()) != ORBX_OK) return rc;
+    rc = orbm_stereo_band_device(c.dev(ok), c.dev(od), c.dev(om), cap, c.dev(om, 2), c.dev(om, 3), 1, rows, scale,
+                                 nlevels, min_d, max_d, c.dev(oo), c.dev(oo, C), c.stream());
+    if (rc != ORBX_OK) return rc;
+    c.fetch(oo, best_idx, (size_t)n_l);
+    c.fetch(oo, best_dist, (size_t)n_l, C);
+    return c.finish();
+}
+
+}  // extern "C"
