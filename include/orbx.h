@@ -806,6 +806,96 @@ double orbx_fixed_atan2(double y, double x);
 /* Test hook: the three correspondences iteration draws r[0..2] select among n (RandomInt and the removal). */
 void orbx_sim3_triplet(int n, const int* r, int* out3);
 
+/* ---- Initializer: the two-view initialisation of Tracking::MonocularInitialization ----
+ * src/Initializer.cc: Initialize (:45-159), FindHomography, FindFundamental, ComputeH21, ComputeF21, CheckHomography,
+ * CheckFundamental, ReconstructF, ReconstructH, DecomposeE, CheckRT, Triangulate and Normalize, statement by
+ * statement, batched over frame pairs: the call that follows SearchForInitialization in src/Tracking.cc.  The
+ * arithmetic order is fixed in DESIGN.md §3 "Initializer arithmetic"; parity with a real OpenCV is unpinned.
+ *
+ * orbm_initialize_device.  Frame table: d_kps[f * cap + i] = mvKeysUn (x and y are read), d_counts[f], nframes.
+ * Pair p: frame 1 (the reference frame) = d_pair_a[p], frame 2 (the current frame) = d_pair_b[p].
+ * d_matches12[p * match_stride + i] = vMatches12[i] as orbm_search_init_batch_device leaves it, -1 none, match_stride
+ * >= cap; never written.  d_draws[p * draws_stride + 8 * it + j] = the raw rand() value (0 .. 2^31 - 1) draw j of
+ * iteration `it` consumes through DUtils::Random::RandomInt, draws_stride >= 8 * max_iterations: SeedRandOnce(0)
+ * seeds once per process and every caller shares the generator, so the values are the caller's.  params: fx, fy,
+ * cx, cy are read (mK).  sigma and max_iterations are the constructor's (1.0, 200); minParallax = 1.0 and
+ * minTriangulated = 50 as Initialize passes them.
+ * Outputs per pair, arrays of npairs entries of the size given:
+ *   status          0, or ORBM_INIT_INVALID / ORBM_INIT_NO_MODEL / ORBM_INIT_FAILED
+ *   model           0 none, 1 the homography (RH > 0.40), 2 the fundamental matrix
+ *   reason          for ORBM_INIT_FAILED the `return false` taken (orbm_init_reason), else 0
+ *   scores[2]       SH, SF
+ *   H21[9], F21[9]  the best-scoring matrices, zeros where no hypothesis scored above 0
+ *   inliersH[cap], inliersF[cap]   vbMatchesInliersH / F as bytes indexed by the frame-1 keypoint, 0 where unmatched
+ *   R21[9], t21[3]  zeros unless status is 0
+ *   p3d[cap * 3], triangulated[cap]   vP3D and vbTriangulated, indexed by the frame-1 keypoint; zeros unless
+ *                   status is 0.  vP3D is written wherever the reference writes it (:1252), vbTriangulated only
+ *                   where cosParallax < 0.99998
+ *   ngood[8], parallax[8]   nGood and parallax of every CheckRT in the reference's order (ReconstructF fills 4)
+ *   nmatches_left   the matches that remain after MonocularInitialization's pruning loop; N unless status is 0
+ *   matches_out[match_stride]   with ORBM_INIT_PRUNE_MATCHES: the row of d_matches12 with that loop applied
+ *                   ("if(mvIniMatches[i]>=0 && !vbTriangulated[i]) mvIniMatches[i]=-1" after a successful
+ *                   Initialize), a plain copy otherwise; may be NULL without the flag
+ * ORBM_INIT_INVALID, and nothing else written: a pair index outside [0, nframes), a count outside [0, cap], a match
+ * outside [-1, count of frame 2), fewer than 8 matches (RandomInt(0, size - 1) is undefined there), max_iterations
+ * outside [1, 4096] (orbm_init_workspace_bytes returns 0 there).  ORBM_INIT_NO_MODEL: no hypothesis scored above 0,
+ * where the reference reads an empty cv::Mat.
+ * d_work of orbm_init_workspace_bytes(npairs, cap, max_iterations) bytes, 16-byte aligned; a workspace sized for more
+ * iterations serves fewer.  ORBX_EINVAL, before any launch, for a null or misaligned argument, cap outside [1,
+ * ORBM_MAX_FEATURES], npairs above 65535, sigma <= 0, an unknown flag or a workspace too small.  Allocates nothing,
+ * asynchronous on `stream`. */
+enum { ORBM_INIT_INVALID = 1, ORBM_INIT_NO_MODEL = 2, ORBM_INIT_FAILED = 4 };   /* status bits */
+enum { ORBM_INIT_PRUNE_MATCHES = 1 };                                          /* flags */
+typedef enum {
+    ORBM_INIT_REASON_NONE = 0,
+    ORBM_INIT_F_AMBIGUOUS = 1,   /* :739  maxGood < nMinGood || nsimilar > 1 */
+    ORBM_INIT_F_PARALLAX = 2,    /* :745-791  the winning candidate's parallax is not above minParallax */
+    ORBM_INIT_H_SINGULAR = 3,    /* :845  d1/d2 < 1.00001 || d2/d3 < 1.00001 */
+    ORBM_INIT_H_TEST = 4         /* :987  the final test fails */
+} orbm_init_reason;
+
+typedef struct {
+    int32_t *status, *model, *reason;
+    float *scores, *H21, *F21;
+    uint8_t *inliersH, *inliersF;
+    float *R21, *t21, *p3d;
+    uint8_t* triangulated;
+    int32_t* ngood;
+    float* parallax;
+    int32_t* nmatches_left;
+    int32_t* matches_out;
+} orbm_init_out;
+
+/* A pure size planner: 0 for what orbm_initialize_device does not accept. */
+size_t orbm_init_workspace_bytes(int npairs, int cap, int max_iterations);
+
+orbx_status orbm_initialize_device(const orbx_keypoint* d_kps, const int* d_counts, int nframes, int cap,
+                                   const int* d_pair_a, const int* d_pair_b, int npairs, const int* d_matches12,
+                                   int match_stride, const int* d_draws, int draws_stride,
+                                   const orbm_pose_params* params, float sigma, int max_iterations, int flags,
+                                   void* d_work, size_t work_bytes, const orbm_init_out* out, void* stream);
+
+/* One pair on host arrays, on HIP device `device`; synchronous.  kps1 (n1), kps2 (n2), matches12 (n1), draws (8 *
+ * max_iterations); `out` points at host arrays of one pair with n1 in the place of cap and of match_stride.  Of an
+ * invalid pair only *out->status is written. */
+orbx_status orbm_initialize(int device, const orbx_keypoint* kps1, int n1, const orbx_keypoint* kps2, int n2,
+                            const int* matches12, const int* draws, const orbm_pose_params* params, float sigma,
+                            int max_iterations, int flags, const orbm_init_out* out);
+
+/* Test hooks, not part of the interface a caller builds on.  orbm_initialize_host: the kernels' own code compiled
+ * for the CPU and run by one lane, the arguments and results of orbm_initialize without a device;
+ * tests/test_initializer.py compares it with its restatement bit for bit. */
+orbx_status orbm_initialize_host(const orbx_keypoint* kps1, int n1, const orbx_keypoint* kps2, int n2,
+                                 const int* matches12, const int* draws, const orbm_pose_params* params, float sigma,
+                                 int max_iterations, int flags, const orbm_init_out* out);
+
+/* mvSets (:88-120) for n matches: sets[8 * it + j] from draws[8 * it + j], RandomInt and the swap-with-back removal.
+ * n >= 8. */
+void orbx_init_sets(int n, const int* draws, int iterations, int* sets);
+
+/* Test hook: acosf as CheckRT's parallax evaluates it (csrc/orbx_math.hpp fixed_acosf). */
+float orbx_fixed_acosf(float x);
+
 /* ---- New MapPoints: the match loop of LocalMapping::CreateNewMapPoints ----
  * src/LocalMapping.cc:284-450, between SearchForTriangulation (orbm_bow_search_device, ORBM_TRIANGULATION) and the
  * MapPoint refresh above.  For every vMatchedPairs entry: the parallax of the two rays, a 4x4 cv::SVD triangulation

@@ -231,6 +231,24 @@ ORBX_HD double fixed_atan2(double y, double x)
     return yneg ? (z - kAT_pi_lo) - kAT_pi : kAT_pi - (z - kAT_pi_lo);
 }
 
+// acosf(x) for the Initializer's parallax angle (DESIGN.md §3 "Initializer arithmetic"): a fixed sequence of double
+// * + and one sqrt that the host and the gfx950 code evaluate alike, rounded to float once.  Abramowitz & Stegun,
+// Handbook of Mathematical Functions, 4.4.46 (from Hastings, Approximations for Digital Computers): for 0 <= x <= 1,
+// arccos x = sqrt(1 - x) * (a0 + a1 x + ... + a7 x^7) + e(x), |e(x)| <= 2 x 10^-8 (stated to one digit: a0 itself is
+// 2.18e-8 below pi / 2); arccos(-x) = pi - arccos x.  |x| > 1 and NaN give NaN (the square root of a negative number).
+constexpr double kAC_0 = 1.5707963050, kAC_1 = -0.2145988016, kAC_2 = 0.0889789874, kAC_3 = -0.0501743046,
+                 kAC_4 = 0.0308918810, kAC_5 = -0.0170881256, kAC_6 = 0.0066700901, kAC_7 = -0.0012624911;
+
+ORBX_HD float fixed_acosf(float xf)
+{
+    const double x = (double)xf;
+    const double a = x < 0.0 ? -x : x;
+    const double p =
+        kAC_0 + a * (kAC_1 + a * (kAC_2 + a * (kAC_3 + a * (kAC_4 + a * (kAC_5 + a * (kAC_6 + a * kAC_7))))));
+    const double r = __builtin_sqrt(1.0 - a) * p;
+    return (float)(x < 0.0 ? kAT_pi - r : r);
+}
+
 // (float)(CV_PI/180.f), src/ORBextractor.cc:131
 constexpr float kFactorPI = (float)(3.1415926535897932384626433832795 / 180.f);
 

@@ -101,6 +101,30 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
     orbm_search_init_batch_device(d_kps, d_desc, d_counts, nframes, cap, d_pair_a, d_pair_b, npairs, rows, cols, 100,
                                   0.9f, 1, d_m12, d_nm, stream);
 
+    // Tracking::MonocularInitialization: Initializer::Initialize on the matches where they lie
+    {
+        orbm_pose_params Pi = {};
+        const int* d_draws = nullptr;   // 8 * 200 rand() values per pair
+        void* d_init_work = nullptr;    // hipMalloc once
+        size_t init_bytes = orbm_init_workspace_bytes(npairs, cap, 200);
+        orbm_init_out d_out = {};       // device arrays, one row per pair
+        orbm_initialize_device(d_kps, d_counts, nframes, cap, d_pair_a, d_pair_b, npairs, d_m12, cap, d_draws, 8 * 200,
+                               &Pi, 1.0f, 200, ORBM_INIT_PRUNE_MATCHES, d_init_work, init_bytes, &d_out, stream);
+        // ... and one pair on host arrays
+        std::vector<int> ini_matches(n, -1), pruned(n), draws(8 * 200), sets(8 * 200);
+        for (int& r : draws) r = rand();
+        std::vector<uint8_t> inlH(n), inlF(n), tri(n);
+        std::vector<float> p3d(3 * n);
+        int status = 0, model = 0, reason = 0, left = 0, ngood8[8];
+        float scores[2], H21[9], F21[9], R21[9], t21[3], parallax8[8];
+        orbm_init_out o = {&status, &model, &reason, scores, H21, F21, inlH.data(), inlF.data(), R21, t21,
+                           p3d.data(), tri.data(), ngood8, parallax8, &left, pruned.data()};
+        orbm_initialize(0, (const orbx_keypoint*)kps.data(), n, (const orbx_keypoint*)kps.data(), n, ini_matches.data(),
+                        draws.data(), &Pi, 1.0f, 200, ORBM_INIT_PRUNE_MATCHES, &o);
+        orbx_init_sets(n, draws.data(), 200, sets.data());
+        if ((status & ORBM_INIT_FAILED) && reason == ORBM_INIT_H_TEST) left = 0;
+    }
+
     // ComputeStereoMatches and its coarse stage
     std::vector<float> mvuRight(n, -1.f), mvDepth(n, -1.f), mvScaleFactors(8, 1.f);
     int ngood = 0;

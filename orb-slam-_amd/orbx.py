@@ -53,6 +53,8 @@ EXPORTED = [
     "orbx_po_sincos_theta3",
     "orbm_sim3_workspace_bytes", "orbm_sim3_ransac_iterations", "orbm_sim3_setup_device", "orbm_sim3_iterate_device",
     "orbm_sim3_solve", "orbm_sim3_solve_host", "orbx_fixed_atan2", "orbx_sim3_triplet",
+    "orbm_init_workspace_bytes", "orbm_initialize_device", "orbm_initialize", "orbm_initialize_host", "orbx_init_sets",
+    "orbx_fixed_acosf",
     "orbm_refresh_map_points_device", "orbm_refresh_map_points", "orbm_triangulate_device", "orbm_triangulate",
     "orbm_local_map_work_bytes", "orbm_local_map_device", "orbm_local_map",
     "orbm_connections_work_bytes", "orbm_update_connections_device", "orbm_update_connections",
@@ -160,6 +162,13 @@ class PoseParams(C.Structure):
                 ("log_scale", C.c_float), ("nlevels", C.c_int32), ("th", C.c_float), ("mono", C.c_int32),
                 ("orb_dist", C.c_int32), ("check_ori", C.c_int32), ("scale", C.c_float * 16),
                 ("inv_sigma2", C.c_float * 16)]
+
+
+class InitOut(C.Structure):
+    """orbm_init_out: the per-pair output arrays of the Initializer (host or device pointers)."""
+    _fields_ = [(n, C.c_void_p) for n in ("status", "model", "reason", "scores", "H21", "F21", "inliersH", "inliersF",
+                                          "R21", "t21", "p3d", "triangulated", "ngood", "parallax", "nmatches_left",
+                                          "matches_out")]
 
 
 def pose_params(K, bounds, scale, inv_sigma2=None, log_scale=None, bf=0.0, th=1.0, mono=False, orb_dist=100,
@@ -319,6 +328,17 @@ def _load():
     L.orbx_fixed_atan2.restype = C.c_double
     L.orbx_sim3_triplet.argtypes = [C.c_int, i32p, i32p]
     L.orbx_sim3_triplet.restype = None
+    L.orbm_init_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.orbm_init_workspace_bytes.restype = C.c_size_t
+    L.orbm_initialize_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int,
+                                         P(PoseParams), C.c_float, C.c_int, C.c_int, vp, C.c_size_t, P(InitOut), vp]
+    for fn in (L.orbm_initialize, L.orbm_initialize_host):
+        fn.argtypes = ([C.c_int] if fn is L.orbm_initialize else []) + [
+            vp, C.c_int, vp, C.c_int, vp, vp, P(PoseParams), C.c_float, C.c_int, C.c_int, P(InitOut)]
+    L.orbx_init_sets.argtypes = [C.c_int, vp, C.c_int, vp]
+    L.orbx_init_sets.restype = None
+    L.orbx_fixed_acosf.argtypes = [C.c_float]
+    L.orbx_fixed_acosf.restype = C.c_float
     L.orbm_refresh_map_points_device.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int,
                                                  C.c_int, P(PoseParams), vp, vp, vp, vp]
     L.orbm_refresh_map_points.argtypes = [C.c_int, C.c_int, vp, u8p, i32p, C.c_int, C.c_int, f32p, u8p, i32p, vp, vp,
@@ -944,6 +964,110 @@ class Sim3Solver:
     def find(self, rand, rand_off, stream=None):
         """Sim3Solver::find: iterate(mRansacMaxIts); needs max_iters_per_call >= max_iterations."""
         return self.iterate(self.max_iterations, rand, rand_off, stream)
+
+
+INIT_INVALID, INIT_NO_MODEL, INIT_FAILED = 1, 2, 4    # orbm_initialize*: status bits
+INIT_PRUNE_MATCHES = 1                                # flag
+INIT_F_AMBIGUOUS, INIT_F_PARALLAX, INIT_H_SINGULAR, INIT_H_TEST = 1, 2, 3, 4   # orbm_init_reason
+# orbm_init_out: (field, dtype, entries per pair; "cap" = one per frame-1 keypoint, "stride" = the match row)
+_INIT_FIELDS = (("status", np.int32, 1), ("model", np.int32, 1), ("reason", np.int32, 1), ("scores", np.float32, 2),
+                ("H21", np.float32, 9), ("F21", np.float32, 9), ("inliersH", np.uint8, "cap"),
+                ("inliersF", np.uint8, "cap"), ("R21", np.float32, 9), ("t21", np.float32, 3),
+                ("p3d", np.float32, "cap3"), ("triangulated", np.uint8, "cap"), ("ngood", np.int32, 8),
+                ("parallax", np.float32, 8), ("nmatches_left", np.int32, 1), ("matches_out", np.int32, "stride"))
+
+
+def fixed_acosf(x):
+    """acosf as the Initializer's parallax evaluates it (host code)."""
+    return lib.orbx_fixed_acosf(float(x))
+
+
+def init_sets(n, draws, iterations):
+    """mvSets of Initializer::Initialize (:88-120) for n matches from 8 raw rand() values per iteration."""
+    r = np.ascontiguousarray(draws, np.int32).reshape(-1)
+    assert n >= 8 and len(r) >= 8 * iterations
+    o = np.zeros((iterations, 8), np.int32)
+    lib.orbx_init_sets(int(n), r.ctypes.data, int(iterations), o.ctypes.data)
+    return o
+
+
+def initialize(kps1, kps2, matches12, draws, params, sigma=1.0, max_iterations=200, prune_matches=False, device=0,
+               on_host=False):
+    """Initializer::Initialize on host arrays (one pair).  kps1 / kps2: mvKeysUn of the reference and the current
+    frame (KEYPOINT_DTYPE); matches12 (n1,) int32 as SearchForInitialization leaves it; draws: 8 * max_iterations raw
+    rand() values; params: PoseParams (fx, fy, cx, cy are read).  on_host=True runs the kernels' code on the CPU
+    (orbm_initialize_host).  Returns a dict: status, and for a valid pair model, reason, scores (2,), H21, F21, R21
+    (9,), t21 (3,), inliersH, inliersF, triangulated (n1,) uint8, p3d (n1, 3), ngood, parallax (8,), nmatches_left and,
+    with prune_matches, matches_out (n1,)."""
+    k1, k2 = (np.ascontiguousarray(k, KEYPOINT_DTYPE).reshape(-1) for k in (kps1, kps2))
+    n1, n2 = len(k1), len(k2)
+    m12 = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+    rd = np.ascontiguousarray(draws, np.int32).reshape(-1)
+    assert len(m12) == n1 and (not 1 <= int(max_iterations) <= 4096 or len(rd) >= 8 * int(max_iterations))
+    if not len(rd):
+        rd = np.zeros(8, np.int32)
+    size = {"cap": max(n1, 1), "cap3": 3 * max(n1, 1), "stride": max(n1, 1)}
+    arr = {f: np.zeros(size.get(k, k), dt) for f, dt, k in _INIT_FIELDS}
+    out = InitOut(**{f: a.ctypes.data for f, a in arr.items()})
+    prm = PoseParams.from_buffer_copy(params)
+    d = lambda a: a.ctypes.data if len(a) else None   # noqa: E731
+    args = (d(k1), n1, d(k2), n2, d(m12), rd.ctypes.data, C.byref(prm), float(sigma), int(max_iterations),
+            INIT_PRUNE_MATCHES if prune_matches else 0, C.byref(out))
+    if on_host:
+        _check("orbm_initialize_host", lib.orbm_initialize_host(*args))
+    else:
+        _check("orbm_initialize", lib.orbm_initialize(device, *args))
+    st = int(arr["status"][0])
+    if st & INIT_INVALID:
+        return dict(status=st)
+    r = dict(status=st, model=int(arr["model"][0]), reason=int(arr["reason"][0]),
+             nmatches_left=int(arr["nmatches_left"][0]), p3d=arr["p3d"][:3 * n1].reshape(n1, 3))
+    for f in ("scores", "H21", "F21", "R21", "t21", "ngood", "parallax"):
+        r[f] = arr[f]
+    for f in ("inliersH", "inliersF", "triangulated"):
+        r[f] = arr[f][:n1]
+    if prune_matches:
+        r["matches_out"] = arr["matches_out"][:n1]
+    return r
+
+
+class Initializer:
+    """A batch of ORB_SLAM2::Initializer::Initialize calls on the device, one per frame pair: owns the workspace and
+    the output tensors (the fields of orbm_init_out, one row per pair).  Tensors live on `device`."""
+
+    def __init__(self, npairs, cap, params, device, match_stride=None, sigma=1.0, max_iterations=200):
+        import torch
+        self.npairs, self.cap, self.max_iterations = int(npairs), int(cap), int(max_iterations)
+        self.match_stride = int(match_stride) if match_stride is not None else self.cap
+        self.sigma = float(sigma)
+        self.params = PoseParams.from_buffer_copy(params)
+        self.work_bytes = lib.orbm_init_workspace_bytes(self.npairs, self.cap, self.max_iterations)
+        if not self.work_bytes and self.npairs:
+            raise OrbxError("orbm_init_workspace_bytes", EINVAL)
+        self.work = torch.zeros((max(self.work_bytes, 16) + 7) // 8, dtype=torch.int64, device=device)
+        size = {"cap": self.cap, "cap3": 3 * self.cap, "stride": self.match_stride}
+        tdt = {np.int32: torch.int32, np.float32: torch.float32, np.uint8: torch.uint8}
+        for f, dt, k in _INIT_FIELDS:
+            setattr(self, f, torch.zeros((self.npairs, size.get(k, k)), dtype=tdt[dt], device=device))
+        self.p3d = self.p3d.view(self.npairs, self.cap, 3)
+        self.out = InitOut(**{f: getattr(self, f).data_ptr() for f, _, _ in _INIT_FIELDS})
+
+    def initialize(self, kps, counts, pair_a, pair_b, matches12, draws, max_iterations=None, prune_matches=False,
+                   stream=None):
+        """kps (B, cap, 7) int32 = mvKeysUn, counts (B,), pair_a / pair_b (npairs,) int32 (reference, current frame),
+        matches12 (npairs, match_stride) int32 as search_for_initialization_batch leaves it, draws (npairs, >= 8 *
+        max_iterations) int32 raw rand() values.  max_iterations at most the constructor's.  Writes the output
+        tensors and returns self."""
+        it = self.max_iterations if max_iterations is None else int(max_iterations)
+        assert kps.shape[1] == self.cap and pair_a.shape[0] == self.npairs and matches12.shape[0] == self.npairs
+        assert matches12.shape[1] == self.match_stride and draws.shape[0] == self.npairs
+        _check("orbm_initialize_device",
+               lib.orbm_initialize_device(_ptr(kps), _ptr(counts), kps.shape[0], self.cap, _ptr(pair_a), _ptr(pair_b),
+                                          self.npairs, _ptr(matches12), self.match_stride, _ptr(draws),
+                                          draws.shape[1], C.byref(self.params), self.sigma, it,
+                                          INIT_PRUNE_MATCHES if prune_matches else 0, _ptr(self.work),
+                                          self.work_bytes, C.byref(self.out), _stream(stream)))
+        return self
 
 
 def refresh_map_points_device(what, kps, desc, counts, pose, kf_bad, obs_ptr, obs, ref, max_obs, params, pts, pdesc,
