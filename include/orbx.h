@@ -896,6 +896,132 @@ void orbx_init_sets(int n, const int* draws, int iterations, int* sets);
 /* Test hook: acosf as CheckRT's parallax evaluates it (csrc/orbx_math.hpp fixed_acosf). */
 float orbx_fixed_acosf(float x);
 
+/* ---- PnPsolver: the EPnP RANSAC of Tracking::Relocalization between SearchByBoW(KF, F) and PoseOptimization ----
+ * src/PnPsolver.cc (constructor :67-110, SetRansacParameters :121-157, iterate :165-258, Refine :260-305,
+ * CheckInliers :308-339, compute_pose and everything under it :375-950), as src/Tracking.cc:1393-1554 drives it,
+ * batched over solvers: one solver is one (frame, candidate KeyFrame) pair.  Every iteration of a call is evaluated
+ * as an independent hypothesis, then the reference's sequential acceptance rule is applied.  The arithmetic order
+ * (EPnP in double, the OpenCV calls as OpenCV 3.x's generic path) is fixed in DESIGN.md §3 "PnP solver arithmetic";
+ * parity with a real OpenCV is unpinned.  The nmatches < 15 discard, the round-robin over the candidates, sFound and
+ * the two follow-up SearchByProjection calls, the nGood thresholds and the copy of the chosen solver's rows into the
+ * frame stay with the caller.
+ *
+ * orbm_pnp_setup_device = the constructor and SetRansacParameters, one solver per pair p: frame d_frame_of[p],
+ * KeyFrame d_kf_of[p].  Frame table: d_kps (mvKeysUn; x, y and octave are read) at f * cap, d_counts[f] features,
+ * nframes.  KeyFrame table: d_kf_mp[kf * cap + i] = GetMapPointMatches()[i] as an index into d_pts, -1 none, nkf rows.
+ * d_match[p * match_stride + iF] = the KeyFrame feature orbm_bow_search_device (ORBM_BOW_KF_F) assigned to frame
+ * feature iF, -1 none, match_stride >= cap: vpMapPointMatches[iF] = d_kf_mp[kf * cap + d_match[..]].  An entry survives
+ * if the MapPoint index is >= 0 and flags bit 0 (!isBad()) of the orbm_map_point is set; the survivors are kept in iF
+ * order in d_work with mvP2D = the keypoint's x, y, mvSigma2 = scale[octave]^2, mvP3Dw = the point's x, y, z and
+ * mvKeyPointIndices = iF.  Of params fx, fy, cx, cy (fu, fv, uc, vc), nlevels and scale[] are read.  mvMaxError =
+ * sigma2 * th2 in float.  d_min_inliers[n] and d_maxits[n], n <= cap, are the adjusted mRansacMinInliers and
+ * mRansacMaxIts for N = n (orbm_pnp_ransac_parameters), filled by the caller once per parameter set: only the last
+ * SetRansacParameters call counts, as every field is overwritten.  max_iterations is the maxIterations of that call.
+ * Outputs: d_n[p] = N, d_iterations[p] = d_best_inliers[p] = 0 (mnIterations, mnBestInliers), d_status[p] = 0 or
+ * ORBM_PNP_INVALID.  Invalid: a frame or KeyFrame slot out of range, a count outside [0, cap], a d_match entry outside
+ * [-1, cap), a d_kf_mp entry outside [-1, nmp), the octave of a survivor outside [0, nlevels), or table entries the
+ * calls cannot run with (d_min_inliers[N] < 4, d_maxits[N] outside [1, max_iterations]).  Of an invalid solver only
+ * d_status[p] is written, and iterate gives it no result.
+ *
+ * orbm_pnp_iterate_device = iterate(nit, bNoMore, vbInliers, nInliers) of every solver.  The reference's loop is
+ * while(mnIterations < mRansacMaxIts || nCurrentIterations < nIterations), an OR: a call consumes max(nit,
+ * mRansacMaxIts - mnIterations) iterations unless it returns through Refine(), a call that does not return through
+ * Refine() always ends with bNoMore, and a solver called again at or past mRansacMaxIts runs exactly nit more.
+ * Iteration k of solver p draws its four points from d_rand[d_rand_off[p] + 4k .. + 3], raw rand() values in [0,
+ * 2^31 - 1], through DUtils::Random::RandomInt and the swap-with-back removal; d_rand holds nrand values and a solver
+ * needs 4 * max(nit, max_iterations) of them from its offset on (an iteration whose draws lie outside d_rand counts
+ * as one without inliers).  An iteration with mnInliersi >= mRansacMinInliers replaces the best when strictly greater
+ * and then calls Refine() on the best set: Refine() succeeds on more than mRansacMinInliers inliers (strict), and the
+ * call returns mRefinedTcw, mvbRefinedInliers and mnRefinedInliers.  On exhaustion the call returns mBestTcw
+ * (unrefined) and the best mask if mnBestInliers >= mRansacMinInliers, else no pose.  Refine() is a function of the
+ * best set alone: it is evaluated where the best changes, and its outcome is kept in the solver between the calls, so
+ * a solver that returned through Refine() returns again at its next qualifying iteration.
+ * Outputs per solver: d_tcw[p * 12] = row-major 3x4 Tcw (the CV_64F -> CV_32F conversion of R, t), all 0 without a
+ * pose: the d_pose_in of orbm_pose_optimization_device at stride 12; d_has_pose[p]; d_inliers[p * cap + iF] =
+ * vbInliers; d_ninliers[p] = nInliers; d_nomore[p] = bNoMore; d_used[p] = the iterations this call consumed (the draws
+ * of the next call start 4 * d_used further); d_frame_mp_out[p * cap + iF] = the MapPoint index of an inlier, else -1
+ * (src/Tracking.cc:1481-1490, the d_frame_mp of orbm_pose_optimization_device).  d_iterations / d_best_inliers are
+ * read and updated.  N < mRansacMinInliers is bNoMore with nothing else done; a negative d_iterations is bNoMore
+ * without a result too.
+ * One place the reference is undefined: qr_solve returns early on eta == 0 and leaves X untouched, an uninitialised
+ * stack array on the first Gauss-Newton step.  Here x is zero at the start of each gauss_newton and keeps its
+ * previous content after an early return; the static A1 / A2 are locals.
+ * d_work of orbm_pnp_workspace_bytes(nsolvers, cap, max_iters_per_call) bytes, 16-byte aligned, keeps the solvers
+ * between the calls; max_iters_per_call >= max(nit, max_iterations) of every iterate call.  ORBX_EINVAL before any
+ * launch for a null or misaligned argument, cap outside [1, ORBM_MAX_FEATURES], nsolvers, nit or max_iterations above
+ * 65535, min_set != 4 or a workspace too small.  Both calls allocate nothing and are asynchronous on `stream`. */
+enum { ORBM_PNP_INVALID = 1 };   /* d_status bits */
+
+size_t orbm_pnp_workspace_bytes(int nsolvers, int cap, int max_iters_per_call);
+
+/* SetRansacParameters for N = n (:129-152), the reference's expressions on the host's libm: int nMinInliers = N *
+ * (float)epsilon, raised to min_inliers and to min_set; float epsilon raised to (float)nMinInliers / N; 1 iteration
+ * when nMinInliers == N, else ceil(log(1 - p) / log(1 - pow(eps, 3))); max(1, min(.., max_iterations)).  A value that
+ * is not a number or outside int converts as x86 does (INT_MIN).  Tracking passes (0.99, 10, 300, 4, 0.5, 5.991). */
+void orbm_pnp_ransac_parameters(int n, double probability, int min_inliers, int max_iterations, int min_set,
+                                float epsilon, int* out_min_inliers, int* out_max_iterations);
+
+orbx_status orbm_pnp_setup_device(const orbx_keypoint* d_kps, const int* d_counts, int nframes, int cap,
+                                  const int* d_kf_mp, int nkf, const orbm_map_point* d_pts, int nmp,
+                                  const int* d_frame_of, const int* d_kf_of, int nsolvers, const int* d_match,
+                                  int match_stride, const orbm_pose_params* params, float th2,
+                                  const int* d_min_inliers, const int* d_maxits, int max_iterations, void* d_work,
+                                  size_t work_bytes, int* d_n, int* d_iterations, int* d_best_inliers, int* d_status,
+                                  void* stream);
+
+orbx_status orbm_pnp_iterate_device(void* d_work, size_t work_bytes, int nsolvers, int cap,
+                                    const orbm_pose_params* params, int min_set, int max_iterations, int nit,
+                                    const int* d_rand, int nrand, const int* d_rand_off, int* d_iterations,
+                                    int* d_best_inliers, float* d_tcw, int* d_has_pose, uint8_t* d_inliers,
+                                    int* d_ninliers, int* d_nomore, int* d_used, int* d_frame_mp_out, void* stream);
+
+/* One solver on host arrays, on HIP device `device`; synchronous: the constructor, SetRansacParameters(probability,
+ * min_inliers, max_iterations, min_set, epsilon, th2) and one iterate(nit).  State in and out: *iterations and
+ * *best_inliers (0, 0 for a new solver) and `state`, orbm_pnp_state_bytes(max(n, nk)) bytes, 8-byte aligned (the best
+ * and the refined pose and masks and Refine()'s outcome; not read when *iterations is 0, always written).  kps: the
+ * frame's n mvKeysUn; kf_mp: the KeyFrame's nk MapPoint indices; match: n ints; rand: 4 * max(nit, max_iterations)
+ * ints.  Outputs: *n_out, tcw (12 floats), *has_pose, inliers (n bytes), *ninliers, *nomore, *used, frame_mp_out (n
+ * ints), *status; of an invalid solver only *status is written. */
+size_t orbm_pnp_state_bytes(int cap);
+
+orbx_status orbm_pnp_solve(int device, const orbx_keypoint* kps, int n, const int* kf_mp, int nk,
+                           const orbm_map_point* pts, int nmp, const int* match, const orbm_pose_params* params,
+                           float th2, double probability, int min_inliers, int max_iterations, int min_set,
+                           float epsilon, int nit, const int* rand, int* iterations, int* best_inliers, void* state,
+                           int* n_out, float* tcw, int* has_pose, uint8_t* inliers, int* ninliers, int* nomore,
+                           int* used, int* frame_mp_out, int* status);
+
+/* Test hooks, not part of the interface a caller builds on (they may change or go without notice).
+ * orbm_pnp_solve_host: the kernels' own code compiled for the CPU and run by one lane, the arguments and results of
+ * orbm_pnp_solve without a device; tests/test_pnp_solver.py compares it with its restatement bit for bit.  trace (may
+ * be NULL with trace_cap 0) receives, for the iterations consumed and then for the Refine() calls, what each
+ * compute_pose met: bit a (a = 1, 2, 3) of a field is find_betas_approx_a's branch. */
+typedef struct {
+    int32_t refine;        /* 0 an iteration, 1 a Refine() */
+    int32_t N;             /* the approximation chosen (1, 2, 3) */
+    int32_t b_neg;         /* b[0] < 0 */
+    int32_t b1_neg;        /* b[1] < 0 (approx 2 and 3) */
+    int32_t sign_flip;     /* solve_for_sign flipped */
+    int32_t det_flip;      /* det < 0 in estimate_R_and_t */
+    int32_t qr_singular;   /* qr_solve returned on eta == 0 */
+    int32_t inliers;       /* mnInliersi of an iteration */
+} orbm_pnp_trace;
+
+orbx_status orbm_pnp_solve_host(const orbx_keypoint* kps, int n, const int* kf_mp, int nk, const orbm_map_point* pts,
+                                int nmp, const int* match, const orbm_pose_params* params, float th2,
+                                double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                                int nit, const int* rand, int* iterations, int* best_inliers, void* state,
+                                int* n_out, float* tcw, int* has_pose, uint8_t* inliers, int* ninliers, int* nomore,
+                                int* used, int* frame_mp_out, int* status, orbm_pnp_trace* trace, int trace_cap,
+                                int* ntrace);
+
+/* Test hooks: the four correspondences iteration draws r[0..3] select among n >= 4 (RandomInt and the removal);
+ * qr_solve of a 6x4 system (A24 and b6 are overwritten; returns 1, or 0 where the reference returns early on eta == 0
+ * and x4 keeps its content); cvSVD(A, D, Ut, 0, CV_SVD_MODIFY_A | CV_SVD_U_T) of a 12x12. */
+void orbx_pnp_quad(int n, const int* r, int* out4);
+int orbx_pnp_qr_solve(double* A24, double* b6, double* x4);
+void orbx_pnp_svd12(const double* A144, double* ut144, double* w12);
+
 /* ---- New MapPoints: the match loop of LocalMapping::CreateNewMapPoints ----
  * src/LocalMapping.cc:284-450, between SearchForTriangulation (orbm_bow_search_device, ORBM_TRIANGULATION) and the
  * MapPoint refresh above.  For every vMatchedPairs entry: the parallax of the two rays, a 4x4 cv::SVD triangulation

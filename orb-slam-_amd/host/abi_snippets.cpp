@@ -409,6 +409,45 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
         if (s3_status & ORBM_SIM3_INVALID) nInliers = 0;
     }
 
+    // Tracking::Relocalization: SearchByBoW(KF, F) -> PnPsolver -> PoseOptimization on one stream
+    const orbm_bow_view *d_view_kf = nullptr, *d_view_f = nullptr;   // one row per candidate KeyFrame
+    const int *d_frame_of = nullptr, *d_kf_of = nullptr, *d_pnp_rand = nullptr, *d_pnp_rand_off = nullptr;
+    int ncands_pnp = 8, nrand = 8 * 4 * 300;
+    int *d_bow_f = nullptr, *d_nbow_f = nullptr, *d_pnp_n = nullptr, *d_pnp_its = nullptr, *d_pnp_best = nullptr;
+    int *d_pnp_status = nullptr, *d_pnp_has = nullptr, *d_pnp_ninl = nullptr, *d_pnp_nomore = nullptr;
+    int *d_pnp_used = nullptr, *d_pnp_frame_mp = nullptr;
+    float* d_pnp_tcw = nullptr;
+    uint8_t* d_pnp_inliers = nullptr;
+    // mRansacMinInliers and mRansacMaxIts per N, once per parameter set; copied to d_pnp_mininl / d_pnp_maxits
+    std::vector<int> pnp_mininl((size_t)cap + 1), pnp_maxits((size_t)cap + 1);
+    for (int k = 0; k <= cap; k++)
+        orbm_pnp_ransac_parameters(k, 0.99, 10, 300, 4, 0.5f, &pnp_mininl[k], &pnp_maxits[k]);
+    const int *d_pnp_mininl = nullptr, *d_pnp_maxits = nullptr;
+    size_t pnp_bytes = orbm_pnp_workspace_bytes(ncands_pnp, cap, 300);
+    void* d_pnp_work = nullptr;   // hipMalloc once
+    orbm_bow_search_device(ORBM_BOW_KF_F, d_view_kf, d_view_f, nullptr, ncands_pnp, max_nodes1, 0.75f, 1, d_bow_f, cap,
+                           d_nbow_f, stream);
+    orbm_pnp_setup_device(d_kps_un, d_counts, nkf, cap, d_kf_mp, nkf, d_mps_rw, nmp, d_frame_of, d_kf_of, ncands_pnp,
+                          d_bow_f, cap, &P, 5.991f, d_pnp_mininl, d_pnp_maxits, 300, d_pnp_work, pnp_bytes, d_pnp_n,
+                          d_pnp_its, d_pnp_best, d_pnp_status, stream);
+    // one round of the while loop (:1456-1552): iterate(5) of every candidate still in play
+    orbm_pnp_iterate_device(d_pnp_work, pnp_bytes, ncands_pnp, cap, &P, 4, 300, 5, d_pnp_rand, nrand, d_pnp_rand_off,
+                            d_pnp_its, d_pnp_best, d_pnp_tcw, d_pnp_has, d_pnp_inliers, d_pnp_ninl, d_pnp_nomore,
+                            d_pnp_used, d_pnp_frame_mp, stream);
+    // ... and one candidate on host arrays: a new solver's first call
+    {
+        std::vector<int> kfmp(n, -1), bowf(n, -1), draws(4 * 300), fmp(n, -1);
+        std::vector<uint8_t> inl(n);
+        std::vector<uint64_t> pnp_state((orbm_pnp_state_bytes(n) + 7) / 8);
+        for (int& r : draws) r = rand();
+        int its = 0, best = 0, N = 0, has_pose = 0, nInliers = 0, bNoMore = 0, used = 0, pnp_status = 0;
+        float Tcw[12];
+        orbm_pnp_solve(0, (const orbx_keypoint*)kps.data(), n, kfmp.data(), n, mps.data(), np, bowf.data(), &P, 5.991f,
+                       0.99, 10, 300, 4, 0.5f, 5, draws.data(), &its, &best, pnp_state.data(), &N, Tcw, &has_pose,
+                       inl.data(), &nInliers, &bNoMore, &used, fmp.data(), &pnp_status);
+        if (pnp_status & ORBM_PNP_INVALID) nInliers = 0;
+    }
+
     // ComputeBoW
     std::vector<int32_t> bw(n), node(n), ptr(n + 1), idx(n);
     std::vector<double> bv(n);

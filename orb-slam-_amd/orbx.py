@@ -55,6 +55,9 @@ EXPORTED = [
     "orbm_sim3_solve", "orbm_sim3_solve_host", "orbx_fixed_atan2", "orbx_sim3_triplet",
     "orbm_init_workspace_bytes", "orbm_initialize_device", "orbm_initialize", "orbm_initialize_host", "orbx_init_sets",
     "orbx_fixed_acosf",
+    "orbm_pnp_workspace_bytes", "orbm_pnp_ransac_parameters", "orbm_pnp_setup_device", "orbm_pnp_iterate_device",
+    "orbm_pnp_state_bytes", "orbm_pnp_solve", "orbm_pnp_solve_host", "orbx_pnp_quad", "orbx_pnp_qr_solve",
+    "orbx_pnp_svd12",
     "orbm_refresh_map_points_device", "orbm_refresh_map_points", "orbm_triangulate_device", "orbm_triangulate",
     "orbm_local_map_work_bytes", "orbm_local_map_device", "orbm_local_map",
     "orbm_connections_work_bytes", "orbm_update_connections_device", "orbm_update_connections",
@@ -339,6 +342,27 @@ def _load():
     L.orbx_init_sets.restype = None
     L.orbx_fixed_acosf.argtypes = [C.c_float]
     L.orbx_fixed_acosf.restype = C.c_float
+    L.orbm_pnp_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.orbm_pnp_workspace_bytes.restype = C.c_size_t
+    L.orbm_pnp_state_bytes.argtypes = [C.c_int]
+    L.orbm_pnp_state_bytes.restype = C.c_size_t
+    L.orbm_pnp_ransac_parameters.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, i32p, i32p]
+    L.orbm_pnp_ransac_parameters.restype = None
+    L.orbm_pnp_setup_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp,
+                                        C.c_int, P(PoseParams), C.c_float, vp, vp, C.c_int, vp, C.c_size_t, vp, vp,
+                                        vp, vp, vp]
+    L.orbm_pnp_iterate_device.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, P(PoseParams), C.c_int, C.c_int, C.c_int,
+                                          vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    for fn in (L.orbm_pnp_solve, L.orbm_pnp_solve_host):
+        fn.argtypes = ([C.c_int] if fn is L.orbm_pnp_solve else []) + [
+            vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, P(PoseParams), C.c_float, C.c_double, C.c_int, C.c_int,
+            C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp] + (
+            [vp, C.c_int, vp] if fn is L.orbm_pnp_solve_host else [])
+    L.orbx_pnp_quad.argtypes = [C.c_int, i32p, i32p]
+    L.orbx_pnp_quad.restype = None
+    L.orbx_pnp_qr_solve.argtypes = [vp, vp, vp]
+    L.orbx_pnp_svd12.argtypes = [vp, vp, vp]
+    L.orbx_pnp_svd12.restype = None
     L.orbm_refresh_map_points_device.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int,
                                                  C.c_int, P(PoseParams), vp, vp, vp, vp]
     L.orbm_refresh_map_points.argtypes = [C.c_int, C.c_int, vp, u8p, i32p, C.c_int, C.c_int, f32p, u8p, i32p, vp, vp,
@@ -963,6 +987,155 @@ class Sim3Solver:
 
     def find(self, rand, rand_off, stream=None):
         """Sim3Solver::find: iterate(mRansacMaxIts); needs max_iters_per_call >= max_iterations."""
+        return self.iterate(self.max_iterations, rand, rand_off, stream)
+
+
+PNP_INVALID = 1    # orbm_pnp_*: status bits
+# Tracking::Relocalization's SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991)
+PNP_TRACKING = dict(probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991)
+PNP_TRACE_DTYPE = np.dtype([(k, np.int32) for k in ("refine", "N", "b_neg", "b1_neg", "sign_flip", "det_flip",
+                                                     "qr_singular", "inliers")])
+
+
+def pnp_ransac_parameters(n, probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5):
+    """(mRansacMinInliers, mRansacMaxIts) of PnPsolver::SetRansacParameters for N = n (src/PnPsolver.cc:129-152)."""
+    a, b = C.c_int(0), C.c_int(0)
+    lib.orbm_pnp_ransac_parameters(int(n), float(probability), int(min_inliers), int(max_iterations), int(min_set),
+                                   float(epsilon), C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def pnp_quad(n, draws):
+    """The four correspondences one iteration's raw rand() draws select among n (RandomInt and the removal)."""
+    r = np.ascontiguousarray(draws, np.int32).reshape(4)
+    o = np.zeros(4, np.int32)
+    lib.orbx_pnp_quad(int(n), r.ctypes.data_as(C.POINTER(C.c_int)), o.ctypes.data_as(C.POINTER(C.c_int)))
+    return [int(v) for v in o]
+
+
+def pnp_qr_solve(A, b, x0=None):
+    """PnPsolver::qr_solve of a 6x4 system (host code).  Returns (x, ok): ok False where the reference returns early on
+    eta == 0, and x is then x0 (zeros by default) unchanged."""
+    a = np.array(A, np.float64).reshape(24)
+    bb = np.array(b, np.float64).reshape(6)
+    x = np.zeros(4) if x0 is None else np.array(x0, np.float64).reshape(4)
+    ok = lib.orbx_pnp_qr_solve(a.ctypes.data, bb.ctypes.data, x.ctypes.data)
+    return x, bool(ok)
+
+
+def pnp_svd12(A):
+    """cvSVD(A, D, Ut, 0, CV_SVD_MODIFY_A | CV_SVD_U_T) of a 12x12 as the PnP solver evaluates it: (Ut, w)."""
+    a = np.ascontiguousarray(A, np.float64).reshape(144)
+    ut, w = np.zeros(144), np.zeros(12)
+    lib.orbx_pnp_svd12(a.ctypes.data, ut.ctypes.data, w.ctypes.data)
+    return ut.reshape(12, 12), w
+
+
+def pnp_solve(kps, kf_mp, pts, match, rand, params, nit, probability=0.99, min_inliers=10, max_iterations=300,
+              min_set=4, epsilon=0.5, th2=5.991, iterations=0, best_inliers=0, state=None, device=0, on_host=False,
+              trace=False):
+    """PnPsolver on host arrays (one frame, one candidate KeyFrame): the constructor, SetRansacParameters and one
+    iterate(nit) that starts from (iterations, best_inliers, state).  kps: the frame's mvKeysUn (KEYPOINT_DTYPE);
+    kf_mp: the KeyFrame's GetMapPointMatches() as int32 rows of pts, -1 none; pts MAP_POINT_DTYPE; match (n,) int32 as
+    bow_search (ORBM_BOW_KF_F) leaves it; rand: at least 4 * max(nit, max_iterations) raw rand() values.
+    on_host=True runs the kernels' code on the CPU (orbm_pnp_solve_host), trace=True also returns its trace.
+    Returns a dict: status, and for a valid solver n, tcw (3, 4) float32 (zeros without a pose), has_pose, inliers (n,)
+    uint8, ninliers, nomore, used, frame_mp (n,) int32, iterations, best_inliers, state (pass it to the next call)."""
+    k = np.ascontiguousarray(kps, KEYPOINT_DTYPE).reshape(-1)
+    km = np.ascontiguousarray(kf_mp, np.int32).reshape(-1)
+    p = np.ascontiguousarray(pts, MAP_POINT_DTYPE).reshape(-1)
+    m = np.ascontiguousarray(match, np.int32).reshape(-1)
+    n, nk = len(k), len(km)
+    slots = max(int(nit), int(max_iterations))
+    rd = np.ascontiguousarray(rand, np.int32).reshape(-1)
+    assert len(m) == n and len(rd) >= 4 * slots
+    nbytes = lib.orbm_pnp_state_bytes(max(n, nk, 1))
+    st = np.zeros((nbytes + 7) // 8, np.int64)
+    if state is not None:
+        assert state.nbytes == st.nbytes
+        st[:] = state
+    tcw = np.zeros(12, np.float32)
+    inl, fmp = np.zeros(max(n, 1), np.uint8), np.full(max(n, 1), -1, np.int32)
+    ints = [C.c_int(v) for v in (iterations, best_inliers, 0, 0, 0, 0, 0, 0, 0)]
+    iv = [C.cast(C.byref(v), C.c_void_p) for v in ints]
+    d = lambda a: a.ctypes.data if a is not None and len(a) else None   # noqa: E731
+    prm = PoseParams.from_buffer_copy(params)
+    args = [d(k), n, d(km), nk, d(p), len(p), d(m), C.byref(prm), float(th2), float(probability), int(min_inliers),
+            int(max_iterations), int(min_set), float(epsilon), int(nit), rd.ctypes.data, iv[0], iv[1], st.ctypes.data,
+            iv[2], tcw.ctypes.data, iv[3], inl.ctypes.data, iv[4], iv[5], iv[6], fmp.ctypes.data, iv[7]]
+    tr = None
+    if on_host:
+        tr = np.zeros(2 * slots + 2, PNP_TRACE_DTYPE)
+        _check("orbm_pnp_solve_host", lib.orbm_pnp_solve_host(*args, tr.ctypes.data, len(tr), iv[8]))
+        tr = tr[:ints[8].value]
+    else:
+        _check("orbm_pnp_solve", lib.orbm_pnp_solve(device, *args))
+    if ints[7].value:
+        return dict(status=ints[7].value)
+    out = dict(status=0, n=ints[2].value, tcw=tcw.reshape(3, 4), has_pose=ints[3].value, inliers=inl[:n],
+               ninliers=ints[4].value, nomore=ints[5].value, used=ints[6].value, frame_mp=fmp[:n],
+               iterations=ints[0].value, best_inliers=ints[1].value, state=st)
+    if trace:
+        out["trace"] = tr
+    return out
+
+
+class PnPsolver:
+    """A batch of ORB_SLAM2::PnPsolver on the device: one solver per (frame, candidate KeyFrame) pair, kept in a
+    workspace between the calls.  setup() is the constructor and SetRansacParameters, iterate(nit, ...) the reference's
+    iterate of every solver, find(...) iterate(mRansacMaxIts).  Tensors live on `device`."""
+
+    def __init__(self, nsolvers, cap, max_iters_per_call, params, device, probability=0.99, min_inliers=10,
+                 max_iterations=300, min_set=4, epsilon=0.5, th2=5.991):
+        import torch
+        self.nsolvers, self.cap, self.max_iters = int(nsolvers), int(cap), int(max_iters_per_call)
+        self.params = PoseParams.from_buffer_copy(params)
+        self.max_iterations, self.min_set, self.th2 = int(max_iterations), int(min_set), float(th2)
+        self.work_bytes = lib.orbm_pnp_workspace_bytes(self.nsolvers, self.cap, self.max_iters)
+        if not self.work_bytes and self.nsolvers:
+            raise OrbxError("orbm_pnp_workspace_bytes", EINVAL)
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)   # noqa: E731
+        self.work = torch.zeros((max(self.work_bytes, 16) + 7) // 8, dtype=torch.int64, device=device)
+        table = [pnp_ransac_parameters(n, probability, min_inliers, max_iterations, min_set, epsilon)
+                 for n in range(self.cap + 1)]
+        self.min_inliers = torch.tensor([t[0] for t in table], dtype=torch.int32, device=device)
+        self.maxits = torch.tensor([t[1] for t in table], dtype=torch.int32, device=device)
+        self.n, self.iterations, self.best_inliers, self.status = (i32(self.nsolvers) for _ in range(4))
+        self.tcw = torch.zeros((self.nsolvers, 12), dtype=torch.float32, device=device)
+        self.inliers = torch.zeros((self.nsolvers, self.cap), dtype=torch.uint8, device=device)
+        self.frame_mp = torch.full((self.nsolvers, self.cap), -1, dtype=torch.int32, device=device)
+        self.has_pose, self.ninliers, self.nomore, self.used = (i32(self.nsolvers) for _ in range(4))
+
+    def setup(self, kps, counts, kf_mp, pts, frame_of, kf_of, match, stream=None):
+        """kps (F, cap, 7) int32 view of KEYPOINT_DTYPE, counts (F,), kf_mp (K, cap) int32, pts (nmp, 12) int32 view of
+        MAP_POINT_DTYPE, frame_of / kf_of (nsolvers,), match (nsolvers, stride) int32 as bow_search (ORBM_BOW_KF_F)
+        leaves it.  Writes n, iterations = best_inliers = 0 and status."""
+        assert kps.shape[1] == self.cap and kf_mp.shape[1] == self.cap
+        assert frame_of.shape[0] == self.nsolvers and match.shape[0] == self.nsolvers
+        _check("orbm_pnp_setup_device",
+               lib.orbm_pnp_setup_device(_ptr(kps), _ptr(counts), kps.shape[0], self.cap, _ptr(kf_mp),
+                                         kf_mp.shape[0], _ptr(pts), pts.shape[0], _ptr(frame_of), _ptr(kf_of),
+                                         self.nsolvers, _ptr(match), match.shape[1], C.byref(self.params), self.th2,
+                                         _ptr(self.min_inliers), _ptr(self.maxits), self.max_iterations,
+                                         _ptr(self.work), self.work_bytes, _ptr(self.n), _ptr(self.iterations),
+                                         _ptr(self.best_inliers), _ptr(self.status), _stream(stream)))
+        return self.n, self.status
+
+    def iterate(self, nit, rand, rand_off, stream=None):
+        """iterate(nit) of every solver: rand int32 raw rand() values, rand_off (nsolvers,) int32 where each solver's
+        draws start (4 per iteration, max(nit, max_iterations) iterations).  Returns (tcw, has_pose, inliers, ninliers,
+        nomore, used, frame_mp); the state tensors iterations / best_inliers are updated."""
+        _check("orbm_pnp_iterate_device",
+               lib.orbm_pnp_iterate_device(_ptr(self.work), self.work_bytes, self.nsolvers, self.cap,
+                                           C.byref(self.params), self.min_set, self.max_iterations, int(nit),
+                                           _ptr(rand), int(rand.numel()), _ptr(rand_off), _ptr(self.iterations),
+                                           _ptr(self.best_inliers), _ptr(self.tcw), _ptr(self.has_pose),
+                                           _ptr(self.inliers), _ptr(self.ninliers), _ptr(self.nomore),
+                                           _ptr(self.used), _ptr(self.frame_mp), _stream(stream)))
+        return self.tcw, self.has_pose, self.inliers, self.ninliers, self.nomore, self.used, self.frame_mp
+
+    def find(self, rand, rand_off, stream=None):
+        """PnPsolver::find: iterate(mRansacMaxIts)."""
         return self.iterate(self.max_iterations, rand, rand_off, stream)
 
 
