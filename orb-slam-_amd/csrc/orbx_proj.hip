@@ -566,10 +566,13 @@ struct LocalMapSearch {
     static __device__ __forceinline__ bool rot(const Params&) { return false; }
     static __device__ __forceinline__ int bin(const Point&, const orbx_keypoint&) { return 0; }
     static __device__ __forceinline__ int oct(const orbx_keypoint& kp) { return kp.octave; }
-    // best (d1, level l1) against the second (d2, l2; 256, -1 = none)
+    // best (d1, level l1) against the second (d2, l2; 256, -1 = none).  A candidate at distance 256 is never
+    // the reference's second (dist < bestDist2 = 256 fails, :100-104): bestLevel2 stays -1, from a list entry
+    // and from a rescan's b2 alike
     static __device__ __forceinline__ bool accept(const Params& P, int d1, int l1, int d2, int l2)
     {
         if (!(d1 <= 100)) return false;   // TH_HIGH
+        if (d2 >= 256) l2 = -1;
         if (l1 == l2 && (float)d1 > P.nnratio * (float)d2) return false;
         return true;
     }
