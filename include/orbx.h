@@ -710,7 +710,7 @@ orbx_status orbm_refresh_map_points(int device, int what, const orbx_keypoint* k
  * CheckInliers :340-364, Project / FromCameraToImage :382-423), as src/LoopClosing.cc:274-323 drives it.  Horn's
  * closed-form 3-point solve (cv::eigen's Jacobi on the 4x4 N, cv::Rodrigues) and the projection test of every
  * hypothesis, batched over solvers and iterations.  The arithmetic order is fixed in DESIGN.md §3 "Sim3 solver
- * arithmetic"; parity with a real OpenCV is unpinned.  OptimizeSim3 stays with the caller.
+ * arithmetic"; parity with a real OpenCV is unpinned.  OptimizeSim3 follows below (orbm_optimize_sim3_device).
  *
  * orbm_sim3_setup_device = the constructor and SetRansacParameters, one solver per pair p: KF1 = d_pair_a[p]
  * (mpCurrentKF), KF2 = d_pair_b[p].  KeyFrame table: the layout of orbm_search_by_sim3_device (d_kps = mvKeysUn,
@@ -805,6 +805,87 @@ double orbx_fixed_atan2(double y, double x);
 
 /* Test hook: the three correspondences iteration draws r[0..2] select among n (RandomInt and the removal). */
 void orbx_sim3_triplet(int n, const int* r, int* out3);
+
+/* ---- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) ----
+ * src/Optimizer.cc:1046-1241, which LoopClosing::ComputeSim3 calls between SearchBySim3 and SearchByProjection(pKF,
+ * Scw, ...) (src/LoopClosing.cc:325-335): one free 7-DoF Sim3 vertex, per correspondence the two projection edges
+ * EdgeSim3ProjectXYZ and EdgeInverseSim3ProjectXYZ with fixed points and Huber kernels, g2o's Levenberg on a dense
+ * 7x7 system with the numeric Jacobian of base_binary_edge.hpp, optimize(5), the first inlier check, optimize(10 or
+ * 5), the second check.  One workgroup per pair; the arithmetic order is fixed in DESIGN.md §3 "Sim3 optimisation
+ * arithmetic"; parity with a real g2o / Eigen build is unpinned.
+ *
+ * orbm_optimize_sim3_device.  KeyFrame and MapPoint tables, pairs and params: those of orbm_sim3_setup_device (of
+ * params fx, fy, cx, cy, nlevels and inv_sigma2[] are read; both cameras share them).  d_sim3_in[p * 13] = s12, R12,
+ * t12 as orbm_sim3_iterate_device writes them: the initial estimate is Sim3(toMatrix3d(R), toVector3d(t), (double)s).
+ * d_matches1[p * match_stride + i1] (in / out) = vpMatches1[i1] as an index into d_pts, -1 none, match_stride >= cap.
+ * th2 and fix_scale: the reference passes 10 and mbFixScale.
+ * Feature i1 of KF1 makes a correspondence when d_matches1 >= 0, pMP1 = d_kf_mp[a * cap + i1] is present and not
+ * bad, pMP2 is not bad and i2 = pMP2->GetIndexInKeyFrame(pKF2) >= 0 (the live observation, as orbm_sim3_setup_device
+ * finds it); any other entry of d_matches1 is left as it is.  An entry is set to -1 where either edge's chi2 exceeds
+ * th2 after a round.
+ * Outputs: d_nin[p] the return value (0 where fewer than 10 correspondences survive the first check); d_sim3_out[p *
+ * 8] doubles qx, qy, qz, qw, tx, ty, tz, s, the g2o::Sim3 itself; d_sim3f_out[p * 13] (may be NULL) floats s, R, t in
+ * the format of d_sim3_in; d_scw[p * 12] (may be NULL) the top three rows of Converter::toCvMat(gScm * gSmw) with
+ * gSmw = Sim3(R2w, t2w, 1.0) (src/LoopClosing.cc:333-335), the pose ORBM_PROJ_SIM3 reads; d_trace[p] (may be NULL);
+ * d_status[p] 0 or ORBM_OPT_SIM3_INVALID.  The three Sim3 outputs are written only where the reference reaches
+ * :1237 (trace rounds == 2); they keep their bits otherwise.
+ * Invalid: what orbm_sim3_setup_device lists (slots, counts, d_kf_mp, a descending d_obs_ptr, an observation idx, an
+ * octave), a d_matches1 entry outside [-1, nmp) and an s12 that is not > 0.  Of an invalid pair only d_status[p] is
+ * written.  ORBX_EINVAL for a null or misaligned argument (d_sim3_out: 8 bytes), cap outside [1, ORBM_MAX_FEATURES],
+ * match_stride < cap or npairs above 65535.  Allocates nothing; asynchronous on `stream`. */
+enum { ORBM_OPT_SIM3_INVALID = 1 };   /* d_status bits */
+
+typedef struct {
+    int32_t iters[2];      /* SparseOptimizer::optimize's iterations of the two rounds */
+    int32_t rejected[2];   /* Levenberg trials rejected and popped */
+    int32_t nbad;          /* nBad of the first check */
+    int32_t ncorr;         /* nCorrespondences */
+    int32_t rounds;        /* rounds run: 0 (no correspondence), 1 (fewer than 10 left) or 2 */
+} orbm_opt_sim3_trace;
+
+orbx_status orbm_optimize_sim3_device(const orbx_keypoint* d_kps, const int* d_counts, int nkf, int cap,
+                                      const float* d_pose, const int* d_kf_mp, const orbm_map_point* d_pts, int nmp,
+                                      const int* d_obs_ptr, const orbm_observation* d_obs,
+                                      const uint8_t* d_obs_erased, const int* d_pair_a, const int* d_pair_b,
+                                      int npairs, const float* d_sim3_in, int* d_matches1, int match_stride, float th2,
+                                      int fix_scale, const orbm_pose_params* params, double* d_sim3_out,
+                                      float* d_sim3f_out, float* d_scw, int* d_nin, orbm_opt_sim3_trace* d_trace,
+                                      int* d_status, void* stream);
+
+/* vpMapPointMatches as src/LoopClosing.cc:313-318 builds it and SearchBySim3 (:323) extends it, on the device:
+ * d_matches1[p * match_stride + i1] = d_inliers12[p * cap + i1] ? d_kf_mp[b * cap + d_bow_match12[p * bow_stride +
+ * i1]] : d_sbs_match12[p * cap + i1] >= 0 ? d_kf_mp[b * cap + d_sbs_match12[p * cap + i1]] : -1, with d_inliers12 of
+ * orbm_sim3_iterate_device, d_bow_match12 the d_match12 given to orbm_sim3_setup_device and d_sbs_match12 the
+ * d_match12 of orbm_search_by_sim3_device.  Every i1 < cap is written: -1 at and past KF1's count, for a feature
+ * index outside KF2's count and for a pair whose slots are outside [0, nkf).  Asynchronous on `stream`. */
+orbx_status orbm_sim3_gather_matches_device(const int* d_kf_mp, const int* d_counts, int nkf, int cap,
+                                            const int* d_pair_a, const int* d_pair_b, int npairs,
+                                            const uint8_t* d_inliers12, const int* d_bow_match12, int bow_stride,
+                                            const int* d_sbs_match12, int* d_matches1, int match_stride, void* stream);
+
+/* One pair on host arrays, on HIP device `device`; synchronous.  KeyFrame 1: kps1, kf_mp1, n1, T1w (12 floats);
+ * KeyFrame 2: kps2, n2, T2w; they count as slots 0 and 1 in the observations.  sim3_in: 13 floats; matches1: n1 ints,
+ * updated in place; sim3_out 8 doubles, sim3f_out 13 floats and scw 12 floats (either may be NULL), written only
+ * where the reference reaches :1237; trace may be NULL.  Of an invalid pair only *status is written. */
+orbx_status orbm_optimize_sim3(int device, const orbx_keypoint* kps1, const int* kf_mp1, int n1, const float* T1w,
+                               const orbx_keypoint* kps2, int n2, const float* T2w, const orbm_map_point* pts, int nmp,
+                               const int* obs_ptr, const orbm_observation* obs, const uint8_t* obs_erased,
+                               const float* sim3_in, int* matches1, float th2, int fix_scale,
+                               const orbm_pose_params* params, double* sim3_out, float* sim3f_out, float* scw,
+                               int* nin, orbm_opt_sim3_trace* trace, int* status);
+
+/* Test hooks, not part of the interface a caller builds on (they may change or go without notice).
+ * orbm_optimize_sim3_host: the kernel's own code compiled for the CPU and run by one lane, the arguments and results
+ * of orbm_optimize_sim3 without a device; tests/test_optimize_sim3.py compares it with its restatement bit for bit. */
+orbx_status orbm_optimize_sim3_host(const orbx_keypoint* kps1, const int* kf_mp1, int n1, const float* T1w,
+                                    const orbx_keypoint* kps2, int n2, const float* T2w, const orbm_map_point* pts,
+                                    int nmp, const int* obs_ptr, const orbm_observation* obs,
+                                    const uint8_t* obs_erased, const float* sim3_in, int* matches1, float th2,
+                                    int fix_scale, const orbm_pose_params* params, double* sim3_out, float* sim3f_out,
+                                    float* scw, int* nin, orbm_opt_sim3_trace* trace, int* status);
+
+/* Test hook: exp as the Sim3 optimiser evaluates it (csrc/orbx_math.hpp fixed_exp). */
+double orbx_fixed_exp(double x);
 
 /* ---- Initializer: the two-view initialisation of Tracking::MonocularInitialization ----
  * src/Initializer.cc: Initialize (:45-159), FindHomography, FindFundamental, ComputeH21, ComputeF21, CheckHomography,

@@ -249,6 +249,45 @@ ORBX_HD float fixed_acosf(float xf)
     return (float)(x < 0.0 ? kAT_pi - r : r);
 }
 
+// exp(x) in double for the Sim3 optimiser's scale update (DESIGN.md §3 "Sim3 optimisation arithmetic"): a fixed
+// sequence of double + - * / that the host and the gfx950 code evaluate alike, for the same reason as
+// po_sincos_theta3.  The published fdlibm scheme: k = the integer nearest x / ln2 (0 for |x| <= ln2 / 2), r = (x -
+// k * ln2_hi) - k * ln2_lo with a two-part ln2 (k * ln2_hi is exact for |k| < 2^11), the degree-5 minimax polynomial
+// in r * r, and the result scaled by 2^k built from its exponent bits.  |x| < 2^-28 gives 1 + x, so fixed_exp(0) is
+// exactly 1.  Domain [-708, 709]: above it +inf, below it 0 (no subnormal results), NaN gives NaN.  Within 1 ulp of
+// glibc on [-5, 5] (tests/test_optimize_sim3.py).
+constexpr double kEX_ln2hi = 6.93147180369123816490e-01, kEX_ln2lo = 1.90821492927058770002e-10,
+                 kEX_invln2 = 1.44269504088896338700e+00;
+constexpr double kEX_P1 = 1.66666666666666019037e-01, kEX_P2 = -2.77777777770155933842e-03,
+                 kEX_P3 = 6.61375632143793436117e-05, kEX_P4 = -1.65339022054652515390e-06,
+                 kEX_P5 = 4.13813679705723846039e-08;
+
+ORBX_HD double fixed_exp(double x)
+{
+    if (x != x) return x;
+    if (x > 709.0) return __builtin_inf();
+    if (x < -708.0) return 0.0;
+    const double ax = x < 0.0 ? -x : x;
+    double hi = x, lo = 0.0;
+    long long k = 0;
+    if (ax > 0.5 * (kEX_ln2hi + kEX_ln2lo)) {
+        k = (long long)(kEX_invln2 * x + (x < 0.0 ? -0.5 : 0.5));
+        const double t = (double)k;
+        hi = x - t * kEX_ln2hi;
+        lo = t * kEX_ln2lo;
+    } else if (ax < 3.7252902984619140625e-09) {   // 2^-28
+        return 1.0 + x;
+    }
+    const double r = hi - lo;
+    const double t = r * r;
+    const double c = r - t * (kEX_P1 + t * (kEX_P2 + t * (kEX_P3 + t * (kEX_P4 + t * kEX_P5))));
+    if (k == 0) return 1.0 - ((r * c) / (c - 2.0) - r);
+    const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
+    union { uint64_t u; double d; } two_k;
+    two_k.u = (uint64_t)(1023 + k) << 52;   // k in [-1022, 1023] on the domain
+    return y * two_k.d;
+}
+
 // (float)(CV_PI/180.f), src/ORBextractor.cc:131
 constexpr float kFactorPI = (float)(3.1415926535897932384626433832795 / 180.f);
 

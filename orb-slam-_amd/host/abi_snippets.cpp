@@ -408,6 +408,27 @@ int snippets(orbx_handle* h, orbx_handle* hl, orbx_handle* hr, orbx_vocabulary* 
                         &nInliers, &bNoMore, &used, &s3_status);
         if (s3_status & ORBM_SIM3_INVALID) nInliers = 0;
     }
+    // ... -> the gather -> OptimizeSim3, whose d_scw SearchByProjection(pKF, Scw, ...) reads
+    int *d_matches1 = nullptr, *d_os_nin = nullptr, *d_os_status = nullptr;
+    double* d_g2o_sim3 = nullptr;
+    float *d_sim3_opt = nullptr, *d_scw = nullptr;
+    orbm_opt_sim3_trace* d_os_trace = nullptr;
+    orbm_sim3_gather_matches_device(d_kf_mp, d_counts, nkf, cap, d_cand_a, d_cand_b, ncands3, d_inliers12, d_bow12, cap,
+                                    d_s3_match12, d_matches1, cap, stream);
+    orbm_optimize_sim3_device(d_kps_un, d_counts, nkf, cap, d_Tcw, d_kf_mp, d_mps_rw, nmp, d_obs_ptr, d_obs,
+                              d_obs_erased, d_cand_a, d_cand_b, ncands3, d_sim3, d_matches1, cap, 10.0f,
+                              /*mbFixScale*/ 0, &P, d_g2o_sim3, d_sim3_opt, d_scw, d_os_nin, d_os_trace, d_os_status,
+                              stream);
+    {
+        std::vector<int> mp1(n, -1), matches1(n, -1);
+        float sim3[13] = {1.0f, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}, sim3_opt[13], Scw[12];
+        double g2oS12[8];
+        int nInliers = 0, os_status = 0;
+        orbm_optimize_sim3(0, (const orbx_keypoint*)kps.data(), mp1.data(), n, T1w, (const orbx_keypoint*)kps.data(), n,
+                           T2w, mps.data(), np, obs_ptr.data(), obs.data(), obs_erased.data(), sim3, matches1.data(),
+                           10.0f, 0, &P, g2oS12, sim3_opt, Scw, &nInliers, nullptr, &os_status);
+        if (os_status & ORBM_OPT_SIM3_INVALID) nInliers = 0;
+    }
 
     // Tracking::Relocalization: SearchByBoW(KF, F) -> PnPsolver -> PoseOptimization on one stream
     const orbm_bow_view *d_view_kf = nullptr, *d_view_f = nullptr;   // one row per candidate KeyFrame

@@ -53,6 +53,8 @@ EXPORTED = [
     "orbx_po_sincos_theta3",
     "orbm_sim3_workspace_bytes", "orbm_sim3_ransac_iterations", "orbm_sim3_setup_device", "orbm_sim3_iterate_device",
     "orbm_sim3_solve", "orbm_sim3_solve_host", "orbx_fixed_atan2", "orbx_sim3_triplet",
+    "orbm_optimize_sim3_device", "orbm_sim3_gather_matches_device", "orbm_optimize_sim3", "orbm_optimize_sim3_host",
+    "orbx_fixed_exp",
     "orbm_init_workspace_bytes", "orbm_initialize_device", "orbm_initialize", "orbm_initialize_host", "orbx_init_sets",
     "orbx_fixed_acosf",
     "orbm_pnp_workspace_bytes", "orbm_pnp_ransac_parameters", "orbm_pnp_setup_device", "orbm_pnp_iterate_device",
@@ -331,6 +333,17 @@ def _load():
     L.orbx_fixed_atan2.restype = C.c_double
     L.orbx_sim3_triplet.argtypes = [C.c_int, i32p, i32p]
     L.orbx_sim3_triplet.restype = None
+    L.orbm_optimize_sim3_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int,
+                                            vp, vp, C.c_int, C.c_float, C.c_int, P(PoseParams), vp, vp, vp, vp, vp, vp,
+                                            vp]
+    L.orbm_sim3_gather_matches_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp,
+                                                  C.c_int, vp]
+    for fn in (L.orbm_optimize_sim3, L.orbm_optimize_sim3_host):
+        fn.argtypes = ([C.c_int] if fn is L.orbm_optimize_sim3 else []) + [
+            vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_float, C.c_int, P(PoseParams),
+            vp, vp, vp, vp, vp, vp]
+    L.orbx_fixed_exp.argtypes = [C.c_double]
+    L.orbx_fixed_exp.restype = C.c_double
     L.orbm_init_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.orbm_init_workspace_bytes.restype = C.c_size_t
     L.orbm_initialize_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int,
@@ -988,6 +1001,102 @@ class Sim3Solver:
     def find(self, rand, rand_off, stream=None):
         """Sim3Solver::find: iterate(mRansacMaxIts); needs max_iters_per_call >= max_iterations."""
         return self.iterate(self.max_iterations, rand, rand_off, stream)
+
+
+OPT_SIM3_INVALID = 1    # orbm_optimize_sim3*: status bits
+OPT_SIM3_TRACE_DTYPE = np.dtype([("iters", "<i4", (2,)), ("rejected", "<i4", (2,)), ("nbad", "<i4"), ("ncorr", "<i4"),
+                                 ("rounds", "<i4")])
+
+
+def fixed_exp(x):
+    """exp as the Sim3 optimiser evaluates it (host code)."""
+    return lib.orbx_fixed_exp(float(x))
+
+
+def optimize_sim3_device(kps, counts, pose, kf_mp, pts, obs_ptr, obs, pair_a, pair_b, sim3_in, matches1, params,
+                         th2=10.0, fix_scale=False, obs_erased=None, sim3_out=None, sim3f_out=None, scw=None, nin=None,
+                         trace=None, status=None, stream=None):
+    """Optimizer::OptimizeSim3 over a batch of KeyFrame pairs.  Tables as Sim3Solver.setup: kps (B, cap, 7) int32,
+    counts (B,), pose (B, 12) float32, kf_mp (B, cap) int32, pts (nmp, 12) int32 view of MAP_POINT_DTYPE, obs_ptr
+    (nmp + 1,), obs (nobs, 2) int32, pair_a / pair_b (npairs,).  sim3_in (npairs, 13) float32 = s12, R12, t12;
+    matches1 (npairs, stride) int32 = vpMatches1 as rows of pts, updated in place.  sim3f_out, scw and trace: a
+    tensor, False for none, None for a new one ((npairs, 13) / (npairs, 12) float32, (npairs, 7) int32 view of
+    OPT_SIM3_TRACE_DTYPE); new Sim3 outputs start as zeros and are written only for the pairs that reach the end.
+    Returns (sim3_out (npairs, 8) float64, sim3f_out, scw, nin, trace, status)."""
+    import torch
+    npairs, cap, dev = pair_a.shape[0], kps.shape[1], kps.device
+    new = lambda cur, shape, dt: torch.zeros(shape, dtype=dt, device=dev) if cur is None else cur   # noqa: E731
+    opt = lambda cur, shape, dt: None if cur is False else new(cur, shape, dt)   # noqa: E731
+    sim3_out = new(sim3_out, (npairs, 8), torch.float64)
+    sim3f_out = opt(sim3f_out, (npairs, 13), torch.float32)
+    scw = opt(scw, (npairs, 12), torch.float32)
+    trace = opt(trace, (npairs, 7), torch.int32)
+    nin = new(nin, (npairs,), torch.int32)
+    status = new(status, (npairs,), torch.int32)
+    prm = PoseParams.from_buffer_copy(params)
+    _check("orbm_optimize_sim3_device",
+           lib.orbm_optimize_sim3_device(_ptr(kps), _ptr(counts), kps.shape[0], cap, _ptr(pose), _ptr(kf_mp), _ptr(pts),
+                                         pts.shape[0], _ptr(obs_ptr), _ptr(obs), _ptr(obs_erased), _ptr(pair_a),
+                                         _ptr(pair_b), npairs, _ptr(sim3_in), _ptr(matches1), matches1.shape[1],
+                                         float(th2), int(bool(fix_scale)), C.byref(prm), _ptr(sim3_out),
+                                         _ptr(sim3f_out), _ptr(scw), _ptr(nin), _ptr(trace), _ptr(status),
+                                         _stream(stream)))
+    return sim3_out, sim3f_out, scw, nin, trace, status
+
+
+def sim3_gather_matches_device(kf_mp, counts, pair_a, pair_b, inliers12, bow_match12, sbs_match12, matches1=None,
+                               stream=None):
+    """vpMapPointMatches of LoopClosing::ComputeSim3 after SearchBySim3: kf_mp (B, cap) int32, inliers12 (npairs,
+    cap) uint8 of Sim3Solver.iterate, bow_match12 (npairs, stride) int32 as given to Sim3Solver.setup, sbs_match12
+    (npairs, cap) int32 of search_by_sim3_batch_device.  Returns matches1 (npairs, cap) int32, rows of pts or -1."""
+    import torch
+    npairs, cap = pair_a.shape[0], kf_mp.shape[1]
+    if matches1 is None:
+        matches1 = torch.empty((npairs, cap), dtype=torch.int32, device=kf_mp.device)
+    _check("orbm_sim3_gather_matches_device",
+           lib.orbm_sim3_gather_matches_device(_ptr(kf_mp), _ptr(counts), kf_mp.shape[0], cap, _ptr(pair_a),
+                                               _ptr(pair_b), npairs, _ptr(inliers12), _ptr(bow_match12),
+                                               bow_match12.shape[1], _ptr(sbs_match12), _ptr(matches1),
+                                               matches1.shape[1], _stream(stream)))
+    return matches1
+
+
+def optimize_sim3(kf1, kf2, T1w, T2w, pts, obs_ptr, obs, sim3_in, matches1, params, th2=10.0, fix_scale=False,
+                  obs_erased=None, device=0, on_host=False):
+    """Optimizer::OptimizeSim3 on host arrays (one pair).  kf1 = (mvKeysUn KEYPOINT_DTYPE, GetMapPointMatches() as
+    int32 rows of pts, -1 none), kf2 = (mvKeysUn,); KeyFrame 1 is slot 0 and KeyFrame 2 slot 1 in obs; sim3_in (13,)
+    float32 = s12, R12, t12; matches1 (n1,) int32 = vpMatches1 as rows of pts.  on_host=True runs the kernel's code on
+    the CPU (orbm_optimize_sim3_host).  Returns a dict: status, and for a valid pair nin, matches1, trace
+    (OPT_SIM3_TRACE_DTYPE scalar), written (the reference reached the end) and sim3 (8,) float64 = qx, qy, qz, qw, t,
+    s, sim3f (13,), scw (12,), which are NaN unless written."""
+    k1, k2 = np.ascontiguousarray(kf1[0], KEYPOINT_DTYPE), np.ascontiguousarray(kf2[0], KEYPOINT_DTYPE)
+    m1 = np.ascontiguousarray(kf1[1], np.int32).reshape(-1)
+    n1, n2 = len(k1), len(k2)
+    p = np.ascontiguousarray(pts, MAP_POINT_DTYPE).reshape(-1)
+    op = np.ascontiguousarray(obs_ptr, np.int32).reshape(-1)
+    ob = np.ascontiguousarray(obs, OBSERVATION_DTYPE).reshape(-1)
+    er = None if obs_erased is None else np.ascontiguousarray(obs_erased, np.uint8).reshape(-1)
+    mm = np.array(matches1, np.int32).reshape(-1)
+    assert len(m1) == n1 and len(mm) == n1 and len(op) == len(p) + 1 and (er is None or len(er) == len(ob))
+    t1, t2 = (np.ascontiguousarray(np.asarray(T, np.float32).reshape(-1)[:12]) for T in (T1w, T2w))
+    si = np.ascontiguousarray(np.asarray(sim3_in, np.float32).reshape(13))
+    so, sf, sc = np.full(8, np.nan), np.full(13, np.nan, np.float32), np.full(12, np.nan, np.float32)
+    tr = np.zeros(1, OPT_SIM3_TRACE_DTYPE)
+    ni, st = C.c_int(0), C.c_int(0)
+    d = lambda a: a.ctypes.data if a is not None and len(a) else None   # noqa: E731
+    prm = PoseParams.from_buffer_copy(params)
+    args = (d(k1), d(m1), n1, t1.ctypes.data, d(k2), n2, t2.ctypes.data, d(p), len(p),
+            op.ctypes.data if len(p) else None, d(ob), d(er), si.ctypes.data, d(mm), float(th2), int(bool(fix_scale)),
+            C.byref(prm), so.ctypes.data, sf.ctypes.data, sc.ctypes.data, C.cast(C.byref(ni), C.c_void_p),
+            tr.ctypes.data, C.cast(C.byref(st), C.c_void_p))
+    if on_host:
+        _check("orbm_optimize_sim3_host", lib.orbm_optimize_sim3_host(*args))
+    else:
+        _check("orbm_optimize_sim3", lib.orbm_optimize_sim3(device, *args))
+    if st.value:
+        return dict(status=st.value)
+    return dict(status=0, nin=ni.value, matches1=mm, trace=tr[0], written=int(tr[0]["rounds"]) == 2, sim3=so,
+                sim3f=sf, scw=sc)
 
 
 PNP_INVALID = 1    # orbm_pnp_*: status bits
